@@ -19,9 +19,15 @@ sequence by oracle/fit_checkpoint.py: trained-like weight statistics) and real c
 ``--scene synthetic``: seeded random weights + random rays (nonrigid_nerf_amd/synthetic.py; the round-1 workload, a
 numerical stress scene: sigma logits ~ N(-2, 6^2) everywhere, so 16-bit rounding flips background decisions).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run sets up, warms up, times ``--steps`` steps, writes the last step's outputs (``--dump-outputs DIR``) and prints
+the line.  Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   "roofline":          the dominant kernel (fine-pass network kernel) against the dense MFMA peak of the dtype, from HIP
-                       events recorded around that kernel on the render stream during the timed steps;
+                       events recorded around that kernel on the render stream during the timed steps.
+Only with ``--full`` (each of these takes runs of its own, after the timed region):
+  "roofline.library_gemm_tflops_same_box": a plain hipBLASLt GEMM timed on the same box;
+  "<other scaling>":   for N > 1, the other scaling of the same job (weak / strong) timed in a second region;
+  extra frames:        rendered after the timed region to keep the GPU busy for ``--min-gpu-seconds`` ("untimed_extra_frames",
+                       0 in a plain run);
   "psnr_vs_oracle_db": PSNR (free_viewpoint_rendering.py:821-828) of this run's precision against the fp32 oracle
                        render of the same rays and weights (all rays, no exclusions), checker use of oracle/ only;
   "train_step":        the reference's training iteration at its batch size (1024 rays, perturb + raw noise, forward +
@@ -51,6 +57,7 @@ PEAK_TFLOPS = {"bf16": 2500.0, "f16": 2500.0, "f32": 157.3}       # dense MFMA, 
 SUSTAINED_MFMA_TFLOPS = {"bf16": (2046.0, 2190.0), "f16": (2046.0, 2190.0)}   # measured: profiles/r04_mfma_shape_power.txt (power-capped clock)
 FITTED = os.path.join(REPO, "tests", "golden", "fitted_latest.tar")
 FIXTURE = os.path.join(REPO, "tests", "golden", "example_sequence_96x72.npz")
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
 
 
 def parse_args():
@@ -85,7 +92,16 @@ def parse_args():
                          "weights; no collective while rendering, ONE all-gather of the uint8 frames at the end of each step")
     ap.add_argument("--no-train-step", action="store_true",
                     help="skip the train_step leg (the native training iteration: 1024 rays forward + backward + Adam, untimed part of the run)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the other scaling (N > 1), PSNR against the oracle, the "
+                         "train_step leg, the library GEMM, the --min-gpu-seconds extra frames and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, "
+                         f"at most {DUMP_LIMIT_BYTES // 10 ** 6} MB in all: a fixed, seeded sample of rows beyond that)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -157,6 +173,32 @@ def _pad_rows(t, rows):
     if t.shape[0] == rows:
         return t
     return torch.cat([t, t[-1:].expand(rows - t.shape[0], -1)], 0)
+
+
+def dump_outputs(out_dir, arrays):
+    """``--dump-outputs``: every array as ``out_dir/<name>.npy``, float64 kept, everything else as float32.  Beyond
+    DUMP_LIMIT_BYTES in all, every array keeps the same fraction of its rows, drawn by a fixed seed (sorted, so a sample is
+    the same rows from run to run and build to build); the row indices go to ``<name>.rows.npy`` beside it."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        if isinstance(t, torch.Tensor):          # (bf16 / f16 tensors have no numpy type: widened on the device side)
+            t = t.detach()
+            a = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        else:
+            a = np.asarray(t)
+        host[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in host.values())
+    # a sampled array costs its kept rows plus 8 bytes of index per kept row, and each of its two files a header
+    frac = (DUMP_LIMIT_BYTES - 2 * 256 * len(host)) / (total + 8 * sum(a.shape[0] for a in host.values() if a.ndim > 0))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * frac))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, f"{name}.rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def fitted_checkpoint_for(args):
@@ -240,7 +282,8 @@ def main():
 
     def timed_region(rays_, api_, n_, profile):
         """args.warmup untimed + args.steps timed passes over `rays_` (n_ rays on this rank), bracketed by barrier +
-        synchronize; returns (max over ranks of the wall time, this rank's own wall time, kernel profile, last image)."""
+        synchronize; returns (max over ranks of the wall time, every rank's own wall time, kernel profile, step function,
+        what the last timed step returned)."""
         gather = None
         if world > 1:
             from nonrigid_nerf_amd.distributed import OverlappedGather
@@ -278,20 +321,25 @@ def main():
             dist.all_gather_into_tensor(allt, t)
             per_rank = [float(x) for x in allt.cpu()]
             dt_max = max(per_rank)
-        return dt_max, per_rank, prof_, step
+        return dt_max, per_rank, prof_, step, img
 
     main_stream = torch.cuda.current_stream(dev)
     t_gpu0 = time.perf_counter()
-    dt, per_rank_dt, prof, step = timed_region(rays, api, n, profile=True)
-    # the other scaling of the same job, for N > 1 (one JSON line carries both): the primary record is `args.scaling`
+    dt, per_rank_dt, prof, step, last = timed_region(rays, api, n, profile=True)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives: batchify_rays' dict (N = 1), the gathered [rgb, disp, acc] rows (N > 1)
+        dump_outputs(args.dump_outputs, last if isinstance(last, dict) else
+                     {"rgb_map": last[:, 0:3], "disp_map": last[:, 3], "acc_map": last[:, 4]})
+    del last
+    # the other scaling of the same job, for N > 1 (one JSON line carries both, --full): the primary record is `args.scaling`
     other = None
-    if world > 1:
+    if world > 1 and args.full:
         other_scaling = "strong" if args.scaling == "weak" else "weak"
         _, _, _, rays_o, latents_o, _ = build_workload(args, rank, world, dev, frame_rays=frame_rays, scaling=other_scaling)
         n_o = int(rays_o.shape[0])
-        dt_o, per_rank_o, _, _ = timed_region(rays_o, {"ray_bending_latents": latents_o}, n_o, profile=False)
+        dt_o, per_rank_o, _, _, _ = timed_region(rays_o, {"ray_bending_latents": latents_o}, n_o, profile=False)
         other = scaling_record(other_scaling, world, n_o, args.steps, dt_o, per_rank_o)
-    else:                # N = 1: one frame on one GPU is both the weak and the strong workload
+    elif world == 1:     # N = 1: one frame on one GPU is both the weak and the strong workload
         other = dict(scaling_record("strong" if args.scaling == "weak" else "weak", 1, n, args.steps, dt, per_rank_dt),
                      note="identical to the other scaling at N = 1 (not run twice)")
     # every rank's own kernel time per step (HIP events around each launch on its render stream): lets a scaling record separate
@@ -314,7 +362,9 @@ def main():
     value = total_rays / dt
 
     extra = {}
-    if rank == 0:
+    extra_frames = 0
+    gemm = None
+    if rank == 0 and args.full:
         with torch.no_grad():
             if not args.no_psnr and world == 1:          # (the accuracy / training / CPU legs belong to the N = 1 line: the other
                 extra["psnr_vs_oracle_db"] = psnr_vs_oracle(args, scene, cfg, rays, latents, api, kw, dev)     # ranks of a multi-GPU run would wait for rank 0)
@@ -323,12 +373,11 @@ def main():
         with torch.no_grad():
             gemm = library_gemm_tflops(dev, args.precision) if world == 1 else None
             # keep the device visibly busy for an external sampler (the timed region alone is < 1 s)
-            extra_frames = 0
             while world == 1 and time.perf_counter() - t_gpu0 < args.min_gpu_seconds:
                 step(0)
                 torch.cuda.synchronize()
                 extra_frames += 1
-
+    if rank == 0:
         k = prof["net_fine"]
         peak = PEAK_TFLOPS[args.precision]
 
@@ -359,10 +408,11 @@ def main():
                     "avg_launch_ms": rf["avg_launch_ms"], "issued_mfma_tflops": rf["issued_mfma_tflops"], "frac_issued_mfma": rf["frac_issued_mfma"],
                     "traffic": traffic, "traffic_unit": traffic_note, "traffic_source": traffic_source,
                     "coarse_pass_incl_bender": coarse_roof,
-                    "kernels_ms_per_step": {nm: round(v["ms"] / args.steps, 4) for nm, v in prof.items() if v["launches"]},
-                    # context, not the peak: what a plain hipBLASLt GEMM sustains on this box right now (the chip
-                    # clocks down under MFMA load)
-                    "library_gemm_tflops_same_box": gemm}
+                    "kernels_ms_per_step": {nm: round(v["ms"] / args.steps, 4) for nm, v in prof.items() if v["launches"]}}
+        if args.full:
+            # context, not the peak: what a plain hipBLASLt GEMM sustains on this box right now (the chip
+            # clocks down under MFMA load)
+            roofline["library_gemm_tflops_same_box"] = gemm
         if traffic is None and "BASELINE config 2" not in workload_label(args, cfg, frame_rays, n, world):
             # a variant run has no PMC pass of its own on file: no traffic keys at all rather than a null that reads like a measurement
             for key in ("traffic", "traffic_unit", "traffic_source"):
@@ -397,7 +447,7 @@ def main():
                "per_rank_kernels_ms_per_step": per_rank_kernels,
                "roofline": roofline}
         res.update(extra)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(scene, cfg, args, rays, latents)
         print(json.dumps(res), flush=True)
 
@@ -452,6 +502,8 @@ def frames_mode(args, rank, world, dev, one_gpu, backend):
     dt_own = time.perf_counter() - t0
     prof = model.profile_end()
     assert rgbs.shape == (F, 384, 512, 3) and rgbs.dtype == np.uint8
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"rgbs": rgbs, "disps": disps})
     kern_ms = sum(v["ms"] for v in prof.values())
     mine = len(frame_shard(F, world, rank))
     per_rank = [(dt_own, kern_ms, mine)]

@@ -9,7 +9,7 @@ TAG=${1:-r03}
 R=$PWD
 mkdir -p $R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-train-step --min-gpu-seconds 0"
+COMMON="--full --no-cpu-baseline --no-train-step --min-gpu-seconds 0"
 run() {   # name, steps, warmup, bench arguments...
     local name=$1 steps=$2 warm=$3; shift 3
     python $R/bench.py --steps $steps --warmup $warm $COMMON "$@" 2> $R/gpurun_out/${TAG}_${name}_bench.err | grep '"metric"' > $R/gpurun_out/${TAG}_${name}_bench.json
