@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define NRNERF_ABI_VERSION 8
+#define NRNERF_ABI_VERSION 9
 /* samples per ray and pass: nrnerf_render and the training entry points (the split fine bender -- nrnerf_merge_rows,
  * nrnerf_composite_args.rank_new -- up to 256 merged samples: 8-bit ranks) */
 #define NRNERF_MAX_SAMPLES 1024
@@ -780,6 +780,79 @@ int nrnerf_composite_backward(const nrnerf_composite_args* args, void* hip_strea
 /* profiling: records hipEvents around each kernel of subsequent nrnerf_render calls on this model */
 int nrnerf_profile_begin(nrnerf_model* model);
 int nrnerf_profile_end(nrnerf_model* model, nrnerf_profile* out);   /* synchronises the recorded events */
+
+/* ABI 9: the images free_viewpoint_rendering.py (fvr) writes for every frame, computed on the device from what a render already holds
+ * there.  The arithmetic follows the reference's numpy dtypes: float32 where numpy stays in float32 (disp / max, 255 * x, the truncation
+ * to uint8), double where it promotes (the volume extent of the correspondence map, the light of the Blinn-Phong shading); IEEE division
+ * and square root, no contraction into fused multiply-adds.  All pointers are DEVICE pointers; every call is asynchronous on the stream
+ * and runs on the device that owns the first output.  Images are row-major [F,H,W] (one channel) or [F,H,W,3] (RGB), uint8.
+ *   disp                fvr:351-359  to8b(disp / max)                                       (rnh:19)
+ *   disp_jet            fvr:361-368  to8b(jet(disp / max)): jet = to8b(matplotlib cm.jet(i)[:3]) for the uint8 index i (rnh:701-715)
+ *   disp_phong          fvr:370-377  to8b(blinn_phong(disp / max))                          (rnh:718-791)
+ *   correspondences     fvr:638-645  to8b(frac(voxels * (p - min_point) / (max_point - min_point)))  (frac: x - trunc(x), negatives clip to 0)
+ *   rigidity / _jet     fvr:665-668  as disp / disp_jet without the normalisation */
+typedef enum nrnerf_visualize_flags {
+    NRNERF_VIS_DISP = 1, NRNERF_VIS_DISP_JET = 2, NRNERF_VIS_DISP_PHONG = 4,
+    NRNERF_VIS_CORRESPONDENCES = 8, NRNERF_VIS_RIGIDITY = 16, NRNERF_VIS_RIGIDITY_JET = 32
+} nrnerf_visualize_flags;
+/* how disp is normalised before the three disparity maps */
+typedef enum nrnerf_visualize_normalize {
+    NRNERF_VIS_NORM_NONE = 0,    /* disp as it is */
+    NRNERF_VIS_NORM_GIVEN = 1,   /* disp[f] / disp_max[f], disp_max given by the caller */
+    NRNERF_VIS_NORM_FRAME = 2,   /* disp[f] / max(disp[f]): computed on the device and written to disp_max[f] (fvr's per-image call) */
+    NRNERF_VIS_NORM_STACK = 3    /* disp[f] / max(disp): one max over all F frames (fvr:724-741, the video), written to every disp_max[f] */
+} nrnerf_visualize_normalize;
+typedef struct nrnerf_visualize_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_visualize_args) */
+    uint32_t flags;             /* bits of nrnerf_visualize_flags: which outputs to write */
+    int32_t n_frames, height, width;
+    int32_t normalize;          /* nrnerf_visualize_normalize */
+    const float* disp;          /* [F,H,W] (the DISP flags) */
+    float* disp_max;            /* [F]: in (NORM_GIVEN) or out (NORM_FRAME / NORM_STACK) */
+    const float* surface_pts;   /* [F,H,W,3] the bent point at each pixel's median sample (NRNERF_VIS_CORRESPONDENCES) */
+    double min_point[3], max_point[3];
+    int32_t voxels;             /* fvr:641: sub-voxels per axis; <= 1 = no tiling */
+    const float* rigidity;      /* [F,H,W] (the RIGIDITY flags) */
+    uint8_t* disp_out;          /* [F,H,W] */
+    uint8_t* disp_jet;          /* [F,H,W,3] */
+    uint8_t* disp_phong;        /* [F,H,W,3]; needs H, W >= 2 (np.gradient) */
+    uint8_t* correspondences;   /* [F,H,W,3] */
+    uint8_t* rigidity_out;      /* [F,H,W] */
+    uint8_t* rigidity_jet;      /* [F,H,W,3] */
+} nrnerf_visualize_args;
+int nrnerf_visualize_frames(const nrnerf_visualize_args* args, void* hip_stream);
+
+/* PSNR and SSIM of (gt, rendered) frame pairs, fvr:813-866.  The mask is the pixels where mask_ref's channel sum is 0 (fvr:819-821: the
+ * first ground-truth frame); they are zeroed in both images.  PSNR = -10 log10(mean over H*W*3 of d^2), d = gt - rendered in float32, the
+ * squares and their sum in double.  SSIM = skimage structural_similarity(data_range=1, gaussian_weights=True, sigma=1.5,
+ * use_sample_covariance=False, multichannel=True, full=True) in double: separable 11-tap Gaussian (truncate 3.5) with scipy's 'reflect'
+ * borders, K1 = 0.01, K2 = 0.03, the mean of the map cropped by 5 pixels per channel, then the mean over channels (NaN when the crop is
+ * empty: H or W <= 10).  16 x 16-pixel tiles with their halo in LDS; per-tile partials in the workspace are summed in a fixed order (no
+ * atomics), so the scores are the same bits on every run.  Error maps (fvr:847-860): mse_map = jet(clip(10 |d| / sqrt(3))), |d| the
+ * float32 norm over the channels; ssim_error_map = jet(1 - mean_c S) over the uncropped map. */
+typedef struct nrnerf_metrics_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_metrics_args) */
+    int32_t n_frames, height, width;
+    const float* gt;            /* [F,H,W,3] */
+    const float* rendered;      /* [F,H,W,3] */
+    const float* mask_ref;      /* [H,W,3] or NULL: no mask */
+    double* psnr;               /* [F] out */
+    double* ssim;               /* [F] out */
+    double* mse;                /* [F] out, or NULL */
+    double* ssim_map;           /* [F,H,W,3] out (skimage's full S), or NULL */
+    uint8_t* mse_error_map;     /* [F,H,W,3] out, or NULL */
+    uint8_t* ssim_error_map;    /* [F,H,W,3] out, or NULL */
+    void* workspace;            /* nrnerf_visualize_workspace_bytes(F, H, W) bytes */
+    size_t workspace_bytes;
+} nrnerf_metrics_args;
+size_t nrnerf_visualize_workspace_bytes(int32_t n_frames, int32_t height, int32_t width);
+int nrnerf_image_metrics(const nrnerf_metrics_args* args, void* hip_stream);
+
+/* Background stability of a fixed-camera sequence (fvr:767-785): per-pixel standard deviation over the frames.  accumulate adds one
+ * frame's float32 rgb [n_values] to sum / sum_sq (double, [n_values], zeroed by the caller before the first frame); finish writes
+ * out_rgb [n_pixels,3] = jet(clip(10 * mean_c std)), std the population deviation (ddof 0) sqrt(max(sum_sq / F - (sum / F)^2, 0)). */
+int nrnerf_stability_accumulate(const float* rgb, int64_t n_values, double* sum, double* sum_sq, void* hip_stream);
+int nrnerf_stability_finish(const double* sum, const double* sum_sq, int32_t n_frames, int64_t n_pixels, uint8_t* out_rgb, void* hip_stream);
 
 /* Host-only packing (no device needed): writes the MFMA-fragment weight stream + unit table + bias
  * table of one pass exactly as nrnerf_model_create uploads them.  which: 0 = coarse, 1 = fine, 2 = fine without the

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # NRNERF_LIB selects an alternative build of the same library (tuning experiments, see csrc/Makefile)
 LIB_PATH = os.environ.get("NRNERF_LIB") or os.path.join(_HERE, "lib", "libnrnerf_hip.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_SAMPLES = 1024        # NRNERF_MAX_SAMPLES (include/nrnerf.h): per ray and pass of nrnerf_render; training: 256
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP, ERR_WORKSPACE, ERR_NOMEM, ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6
 PRECISIONS = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "f16": 2, "fp16": 2, "float16": 2}
@@ -291,6 +291,26 @@ class CompositeArgs(C.Structure):
                 ("d_raw4", C.c_void_p), ("z_new", C.c_void_p), ("rank_new", C.c_void_p)]
 
 
+# ABI 9: the images and scores of free_viewpoint_rendering.py (nonrigid_nerf_amd/visualize.py)
+VIS_DISP, VIS_DISP_JET, VIS_DISP_PHONG, VIS_CORRESPONDENCES, VIS_RIGIDITY, VIS_RIGIDITY_JET = 1, 2, 4, 8, 16, 32
+VIS_NORM_NONE, VIS_NORM_GIVEN, VIS_NORM_FRAME, VIS_NORM_STACK = 0, 1, 2, 3
+
+
+class VisualizeArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("n_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("normalize", C.c_int32), ("disp", C.c_void_p), ("disp_max", C.c_void_p), ("surface_pts", C.c_void_p),
+                ("min_point", C.c_double * 3), ("max_point", C.c_double * 3), ("voxels", C.c_int32), ("rigidity", C.c_void_p),
+                ("disp_out", C.c_void_p), ("disp_jet", C.c_void_p), ("disp_phong", C.c_void_p), ("correspondences", C.c_void_p),
+                ("rigidity_out", C.c_void_p), ("rigidity_jet", C.c_void_p)]
+
+
+class MetricsArgs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_frames", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("gt", C.c_void_p), ("rendered", C.c_void_p), ("mask_ref", C.c_void_p), ("psnr", C.c_void_p), ("ssim", C.c_void_p),
+                ("mse", C.c_void_p), ("ssim_map", C.c_void_p), ("mse_error_map", C.c_void_p), ("ssim_error_map", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
 EXPORTS = {
     "nrnerf_abi_version": (C.c_int, []),
     "nrnerf_strerror": (C.c_char_p, [C.c_int]),
@@ -339,6 +359,11 @@ EXPORTS = {
     "nrnerf_composite_backward": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
     "nrnerf_profile_begin": (C.c_int, [C.c_void_p]),
     "nrnerf_profile_end": (C.c_int, [C.c_void_p, C.POINTER(Profile)]),
+    "nrnerf_visualize_frames": (C.c_int, [C.POINTER(VisualizeArgs), C.c_void_p]),
+    "nrnerf_visualize_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "nrnerf_image_metrics": (C.c_int, [C.POINTER(MetricsArgs), C.c_void_p]),
+    "nrnerf_stability_accumulate": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrnerf_stability_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "nrnerf_pack_host": (C.c_int, [C.POINTER(ModelDesc), C.c_int, C.POINTER(PackedInfo), C.c_void_p, C.c_size_t,
                                    C.POINTER(C.c_uint32), _fp]),
 }

@@ -77,9 +77,94 @@ def _gather_frames(stack, n_frames, world, per, group, dst):
     return full.index_select(0, order)
 
 
+VISUALIZATIONS = ("disp", "disp_jet", "disp_phong", "correspondences", "rigidity", "rigidity_jet")
+
+
+def _extras_plan(visualizations, volume_extent, metrics, stability, gt_imgs, render_kwargs, frame_fn):
+    """What render_path's extensions ask for, checked before anything renders; None when nothing is asked."""
+    if isinstance(visualizations, str):
+        visualizations = (visualizations,)
+    vis = tuple(visualizations or ())
+    has_bender = True
+    if frame_fn is None:
+        rb = getattr(render_kwargs.get("network_fn"), "ray_bender", None)
+        has_bender = bool(rb) and rb[0] is not None
+    if "all" in vis:
+        vis = tuple(v for v in VISUALIZATIONS if has_bender or not v.startswith("rigidity")) + tuple(v for v in vis if v != "all")
+    vis = tuple(dict.fromkeys(vis))
+    bad = [v for v in vis if v not in VISUALIZATIONS]
+    if bad:
+        raise ValueError(f"unknown visualizations {bad} (one of {VISUALIZATIONS} or 'all')")
+    if not vis and not metrics and not stability:
+        return None
+    if any(v.startswith("rigidity") for v in vis) and not has_bender:
+        raise ValueError("rigidity maps need a model with a ray bender (this one has none: no rigidity to show)")
+    extent = None
+    if "correspondences" in vis:
+        from . import visualize as V
+        if volume_extent is not None and not isinstance(volume_extent, (tuple, list)):
+            volume_extent = V.volume_extent_of(volume_extent)
+        if volume_extent is None:
+            raise ValueError("the correspondence map needs volume_extent=(min_point, max_point) (or a checkpoint whose scripts_dict has them)")
+        extent = (np.asarray(volume_extent[0], dtype=np.float64).reshape(3), np.asarray(volume_extent[1], dtype=np.float64).reshape(3))
+    if metrics and gt_imgs is None:
+        raise ValueError("metrics=True needs gt_imgs")
+    return {"vis": vis, "extent": extent, "metrics": bool(metrics), "gt": gt_imgs, "mask": None, "stability": None if not stability else True,
+            "surface": any(v in ("correspondences", "rigidity", "rigidity_jet") for v in vis), "scores": []}
+
+
+def _frame_extras(ex, i, out, H, W, dev):
+    """Frame i's maps on the current (compute) stream, as uint8 CUDA tensors without the frame axis."""
+    from . import visualize as V
+    maps = {}
+    vis = ex["vis"]
+    dk = tuple(k for k, name in (("disp", "disp"), ("jet", "disp_jet"), ("phong", "disp_phong")) if name in vis)
+    if dk:
+        maps.update(V.disparity_maps(out["disp_map"].view(H, W), kinds=dk, normalize="frame"))
+    if "correspondences" in vis:
+        maps["correspondences"] = V.correspondence_rgb(out["surface_pts"].view(H, W, 3), ex["extent"][0], ex["extent"][1])
+    rk = tuple(k for k in ("rigidity", "rigidity_jet") if k in vis)
+    if rk:
+        maps.update(V.rigidity_maps(out["surface_rigidity"].view(H, W), kinds=rk))
+    rgb = out["rgb_map"].view(H, W, 3)
+    if ex["metrics"]:
+        # (host frames through pinned memory: a pageable upload would hold the host until the render queued before it is done)
+        up = lambda a: torch.as_tensor(a).to(torch.float32).reshape(H, W, 3).contiguous().pin_memory().to(dev, non_blocking=True)
+        if ex["mask"] is None:
+            ex["mask"] = up(ex["gt"][0])
+        gt = up(ex["gt"][i])
+        m = V.metrics_on_device(gt, rgb, mask_ref=ex["mask"], error_maps=True)
+        ex["scores"].append((i, m["psnr"], m["ssim"]))
+        maps["mse_error"], maps["ssim_error"] = m["mse_error"], m["ssim_error"]
+    if ex["stability"] is not None:
+        if ex["stability"] is True:
+            ex["stability"] = V.BackgroundStability()
+        ex["stability"].add(rgb)
+    return {k: v[0] for k, v in maps.items()}            # (every map above is a stack of this one frame)
+
+
+def _finish_extras(ex, my_maps, mine):
+    """The extra element of render_path's return value."""
+    res = {}
+    for k in (my_maps[0] if my_maps else {}):
+        frames = [m[k] for m in my_maps]
+        res[k] = np.stack(frames, 0) if len({f.shape for f in frames}) == 1 else frames
+    if ex["metrics"]:
+        from . import visualize as V
+        order = [i for i, _, _ in ex["scores"]]
+        psnr = [float(p.item()) for _, p, _ in ex["scores"]]
+        ssim = [float(s.item()) for _, _, s in ex["scores"]]
+        sc = V.scores_json(psnr, ssim)
+        res["scores"] = {**{order[j]: sc[j] for j in range(len(order))}, **{k: v for k, v in sc.items() if isinstance(k, str)}}
+    if ex["stability"] is not None and ex["stability"] is not True:
+        res["stability"] = ex["stability"].finish().cpu().numpy()
+    return res
+
+
 def render_path(render_poses, intrinsics, chunk, render_kwargs, ray_bending_latents, gt_imgs=None, savedir=None,
                 render_factor=0, detailed_output=False, parallelized_render_function=None, surface_outputs=False,
-                rgb_dtype="float32", device=None, group=None, gather="all", _frame_fn=None):
+                rgb_dtype="float32", device=None, group=None, gather="all", _frame_fn=None, visualizations=(), volume_extent=None,
+                metrics=False, stability=False):
     """Signature and return value of reference ``render_path`` (train.py:419-431, 547-553).
 
     ``render_kwargs`` is the dict ``create_nerf`` builds (train.py:698-719) plus ``near`` / ``far``; the networks
@@ -105,6 +190,16 @@ def render_path(render_poses, intrinsics, chunk, render_kwargs, ray_bending_late
     rank returns its own frames (in its own order ``frame_shard(F, G, r)``).  Per-sample details / surface outputs are never
     gathered (15 KB per ray): with ``gather`` the list has one entry per frame, ``None`` for frames another rank rendered.
     The frames of a gathered sequence must share one image size.
+
+    Visualisations (extension; free_viewpoint_rendering.py's per-frame images, ``nonrigid_nerf_amd.visualize``): ``visualizations`` names
+    maps among ``VISUALIZATIONS`` ("all" = every one the model has); ``volume_extent`` = ``(min_point, max_point)`` or a checkpoint whose
+    ``scripts_dict`` holds them (needed by "correspondences"); ``metrics=True`` scores each frame against ``gt_imgs[i]`` (fvr:787-876, the
+    mask from ``gt_imgs[0]``) and adds the two error maps; ``stability=True`` adds the background-stability map of the frames (fvr:767-785).
+    Any of them appends ONE element to the return value: a dict of uint8 stacks ``[F,H,W(,3)]`` keyed by map name, "mse_error" /
+    "ssim_error", "stability" [H,W,3] and "scores" (fvr's scores.json layout).  Each frame's maps are computed on the compute stream right
+    after its render and travel with the frame on the copy stream; per-sample tensors never leave the device.  The disparity maps are
+    normalised per frame, as fvr's image files.  With ``group`` the extras need ``gather=None`` (gathering them raises
+    NotImplementedError) and cover this rank's frames.  Rigidity maps need a model with a ray bender (ValueError otherwise).
     """
     if rgb_dtype not in ("float32", "uint8"):
         raise ValueError("rgb_dtype must be 'float32' or 'uint8'")
@@ -121,6 +216,7 @@ def render_path(render_poses, intrinsics, chunk, render_kwargs, ray_bending_late
                 s[k] = intrin[k] / render_factor
             scaled.append(s)
         intrinsics = scaled
+    extras = _extras_plan(visualizations, volume_extent, metrics, stability, gt_imgs, render_kwargs, _frame_fn)
     world, rank = 1, 0
     if group is not None:
         import torch.distributed as dist
@@ -145,6 +241,11 @@ def render_path(render_poses, intrinsics, chunk, render_kwargs, ray_bending_late
     cuda = dev.type == "cuda"
     copy_stream = torch.cuda.Stream(device=dev) if cuda else None
     sharded_gather = world > 1 and gather is not None
+    if extras is not None and sharded_gather:
+        raise NotImplementedError("visualizations / metrics / stability of a frame-sharded sequence need gather=None")
+    if extras is not None and not cuda:
+        raise ValueError("visualizations / metrics / stability run on a GPU")
+    surface = surface_outputs or (extras is not None and extras["surface"])
     stack_rgb = stack_disp = None          # (sharded + gather) this rank's frames, kept on the device until the one collective
     pending = []          # (pinned rgb, pinned disp, event, details)
     with torch.no_grad():
@@ -157,7 +258,7 @@ def render_path(render_poses, intrinsics, chunk, render_kwargs, ray_bending_late
             else:
                 rays = generate_rays(torch.as_tensor(c2w)[:3, :4], intrin, near, far, use_viewdirs, dev)
                 api = {"ray_bending_latents": code.expand(H * W, code.shape[-1])}          # stride-0 view, never materialised
-                out = R.batchify_rays(rays, api, chunk=chunk, detailed_output=detailed_output, _surface=surface_outputs, **kw)
+                out = R.batchify_rays(rays, api, chunk=chunk, detailed_output=detailed_output, _surface=surface, **kw)
             rgb_d = out["rgb_map"]
             if rgb_dtype == "uint8":
                 rgb_d = (255 * rgb_d.clamp(0, 1)).to(torch.uint8)          # to8b: clip, scale, truncate
@@ -171,6 +272,7 @@ def render_path(render_poses, intrinsics, chunk, render_kwargs, ray_bending_late
                 stack_rgb[slot].copy_(rgb_d.view(H, W, 3))
                 stack_disp[slot].copy_(out["disp_map"].view(H, W))
             keep_local = not sharded_gather
+            maps_d = _frame_extras(extras, i, out, H, W, dev) if extras is not None else {}
             if cuda:
                 done = torch.cuda.Event()
                 done.record(torch.cuda.current_stream(dev))
@@ -187,6 +289,10 @@ def render_path(render_poses, intrinsics, chunk, render_kwargs, ray_bending_late
                     rgb_h, disp_h = host((H, W, 3), rgb_d.dtype), host((H, W), torch.float32)
                     rgb_h.copy_(rgb_d.view(H, W, 3), non_blocking=True)
                     disp_h.copy_(out["disp_map"].view(H, W), non_blocking=True)
+                maps_h = {}
+                for k, v in maps_d.items():
+                    maps_h[k] = host(tuple(v.shape), v.dtype)
+                    maps_h[k].copy_(v, non_blocking=True)
                 details = None
                 if detailed_output or surface_outputs:
                     details = {}
@@ -203,12 +309,13 @@ def render_path(render_poses, intrinsics, chunk, render_kwargs, ray_bending_late
                     ev = torch.cuda.Event()
                     ev.record(copy_stream)
             if cuda:
-                for t in out.values():
+                for t in list(out.values()) + list(maps_d.values()):
                     t.record_stream(copy_stream)
-            pending.append((rgb_h, disp_h, ev, details))
+            pending.append((rgb_h, disp_h, ev, details, maps_h))
     want_details = detailed_output or surface_outputs
     rgbs, disps, my_details = [], [], []
-    for rgb_h, disp_h, ev, details in pending:
+    my_maps = []
+    for rgb_h, disp_h, ev, details, maps_h in pending:
         if ev is not None:
             ev.synchronize()
         if rgb_h is not None:
@@ -216,6 +323,7 @@ def render_path(render_poses, intrinsics, chunk, render_kwargs, ray_bending_late
             disps.append(disp_h.numpy())
         if want_details:
             my_details.append({k: v.numpy() for k, v in details.items()})
+        my_maps.append({k: v.numpy() for k, v in maps_h.items()})
     if sharded_gather:
         if stack_rgb is None:           # more ranks than frames: this rank rendered nothing; the block size comes from the arguments
             per = (n_frames + world - 1) // world
@@ -240,6 +348,7 @@ def render_path(render_poses, intrinsics, chunk, render_kwargs, ray_bending_late
         H, W = (int(intrinsics[0]["height"]), int(intrinsics[0]["width"])) if n_frames else (0, 0)
         rgbs = np.zeros((0, H, W, 3), dtype=np.uint8 if rgb_dtype == "uint8" else np.float32)
         disps = np.zeros((0, H, W), dtype=np.float32)
-    if want_details:
-        return rgbs, disps, my_details
-    return rgbs, disps
+    res = (rgbs, disps, my_details) if want_details else (rgbs, disps)
+    if extras is not None:
+        res = res + (_finish_extras(extras, my_maps, mine),)
+    return res
