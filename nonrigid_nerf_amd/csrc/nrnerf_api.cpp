@@ -16,6 +16,7 @@
 #include <mutex>
 #include <new>
 #include <stdexcept>
+#include <type_traits>
 #include <vector>
 
 #include "nrnerf.h"
@@ -960,7 +961,77 @@ struct PassDev {
     size_t n_elems = 0;
 };
 
+// ---- the packed weight images of a model handle: pack_images() is the one place that says which exist, how each is packed and what
+// metadata goes with it; create / update / destroy and the device-side re-pack iterate the slots
+enum ImageSlot : int {
+    IMG_COARSE, IMG_FINE, IMG_FINE_TRUNK, IMG_COARSE_TRUNK, IMG_BEND_ONLY, IMG_FINE_TRUNK_X16, IMG_COARSE_TRUNK_X16, IMG_BEND_X16,
+    IMG_COARSE_BWD, IMG_FINE_BWD, IMG_COARSE_TRAIN, IMG_FINE_TRAIN, IMG_BEND_TRAIN_FWD, IMG_BEND_TRAIN_BWD,
+    IMG_GEN_BEND, IMG_GEN_COARSE, IMG_GEN_FINE, IMG_GX_COARSE, IMG_GX_FINE, IMG_GEN_COARSE_BWD, IMG_GEN_FINE_BWD, IMG_GX_COARSE_BWD, IMG_GX_FINE_BWD,
+    IMG_COUNT
+};
+// an image as the host packs it
+struct Image {
+    ImageSlot slot;
+    PackedPass pk;
+    double algo_flops = 0, mfma_flops = 0;      // per sample, as PassDev
+    int output_ch = 4;
+    GenArgs proto{};                             // layer programs: the program
+    GxMeta gx{};                                 // width-class trunks: the kernel's run-time parameters
+    explicit Image(ImageSlot s) : slot(s) {}
+};
+// ... and on the device
+struct ImageDev : PassDev { GenArgs prog{}; GxMeta gx{}; };
+// what the training entry points of a generic handle know about a trunk
+struct GenTrainNet { int W = 0, D = 0, dv = 0, draw_col = 0, in_w = 0, lat = 0, skip = 0, views = 0; };
+// what a model description makes of a handle besides its images (pack_images); a refresh needs a description with the same traits
+// (ints throughout, flags included: no padding, so two records are the same model exactly when their bytes are equal -- same_traits)
+struct ModelTraits {
+    int precision = 0, has_bend = 0, views = 0, arch_id = 0, needs_latents = 0, latent_size = 0, exact = 0;
+    int fine_is_coarse = 0;       // no fine network: the coarse network's images serve both passes
+    int split_ok = 0;             // split-bender images (fine_trunk, coarse_trunk, bend_only)
+    int train_ok = 0;             // see training_eligible
+    int bend_train_ok = 0;        // the bender's training images
+    int generic = 0;              // architecture outside the compiled set: layer programs
+    int gen_compiled_bender = -1; // generic, >= 0: the bender has one of the compiled shapes (0: 5 x 64, 1: 7 x 64; latent 32, rigidity 3 x 32) and the
+                                  // stand-alone bender kernel (nrnerf_bend.h, image `bend_only`) takes the passes without detail outputs
+    int gen_train_ok = 0;
+    GenTrainNet gen_tn[2];        // [coarse, fine]
+};
+static_assert(std::has_unique_object_representations_v<ModelTraits>, "ModelTraits is compared as bytes: no padding, no floating point");
+bool same_traits(const ModelTraits& a, const ModelTraits& b) { return std::memcmp(&a, &b, sizeof(ModelTraits)) == 0; }
+
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// work counters of the 16x16x32 stand-alone bender (BendArgs::work_counter): two launches per call, up to 512 counters each, 64 bytes apart
+constexpr int BEND_COUNTERS_PER_LAUNCH = 512;
+// ... and behind them one counter per 16x16x32 trunk launch (NetArgs::work_counter), 64 bytes apart
+constexpr size_t BEND_COUNTER_BYTES = (size_t)2 * BEND_COUNTERS_PER_LAUNCH * 64 + 256;
+
+// The workspace of a render call: ten slots, each 256-byte aligned, and the work counters behind them.  Byte offsets from the workspace's
+// base; a slot the call does not have (`present` false) takes no room.  nrnerf_workspace_bytes answers `total`, nrnerf_render takes its
+// pointers from the same object.
+struct WorkspaceLayout {
+    size_t raw_c, z_fine, raw_f, bent4, z_coarse, bent_c, z_new, rank_new, jdirs, counters, total = 0;
+    WorkspaceLayout(int n_rays, int n_samples, int n_importance, bool jacobian_dirs) {
+        const size_t N = (size_t)n_rays, S = (size_t)n_samples, I = (size_t)n_importance, SF = S + I;
+        auto slot = [&](size_t bytes, bool present = true) {
+            const size_t at = total;
+            if (present) total += align_up(bytes, 256);
+            return at;
+        };
+        raw_c = slot(N * S * 4 * sizeof(float));                    // raw outputs of the coarse pass
+        z_fine = slot(N * SF * sizeof(float), I > 0);               // merged depths ...
+        raw_f = slot(N * SF * 4 * sizeof(float), I > 0);            // ... and raw outputs of the fine pass
+        bent4 = slot(N * SF * 4 * sizeof(float));                   // bent point + rigidity of the final pass (surface reduction, split-bender path)
+        z_coarse = slot(N * S * sizeof(float));                     // jittered coarse depths (perturb > 0)
+        bent_c = slot(N * S * 4 * sizeof(float), I > 0);            // split-bender path: coarse bent points,
+        z_new = slot(N * I * sizeof(float), I > 0);                 //   depths ...
+        rank_new = slot(N * I, I > 0);                              //   ... and rows of the new samples
+        jdirs = slot(N * SF * 3 * sizeof(float), jacobian_dirs);    // per-sample Jacobian directions of a pass (generic handle, exact view directions)
+        counters = slot(BEND_COUNTER_BYTES);                        // work counters of the stand-alone bender and 16x16x32 trunk launches
+    }
+    template <class T> T* at(void* base, size_t offset, bool present = true) const { return present ? (T*)((char*)base + offset) : nullptr; }
+};
 
 // makes `want` the calling thread's current device for the lifetime of the guard (restored on every exit path)
 struct DeviceGuard {
@@ -976,47 +1047,37 @@ struct DeviceGuard {
 
 }  // namespace
 
-struct nrnerf_model {
-    int device = 0, precision = 0, has_bend = 0, views = 0, arch_id = 0, needs_latents = 0, num_cus = 0, latent_size = 0, exact = 0;
-    PassDev coarse, fine;
-    bool fine_is_coarse = false;
+struct nrnerf_model : ModelTraits {
+    // `fine` / `gen_fine` resolve to the coarse network's image when the model has no fine network (one network for both passes)
+    explicit nrnerf_model(const ModelTraits& t)
+        : ModelTraits(t), fine(img[t.fine_is_coarse ? IMG_COARSE : IMG_FINE]), gen_fine(img[t.fine_is_coarse ? IMG_GEN_COARSE : IMG_GEN_FINE]) {}
+    int device = 0, num_cus = 0;
+    ImageDev img[IMG_COUNT];      // every packed weight image, by slot (pack_images says which exist); the names below are what the launch code uses
+    ImageDev &coarse = img[IMG_COARSE], &fine;
     // split-bender path (bender; finite-difference view directions if any): the fine network WITHOUT the bender layers (its input points
     // come from the stand-alone bender kernel) and the bender + rigidity layers alone
-    PassDev fine_trunk, coarse_trunk, bend_only;
-    bool split_ok = false;
+    ImageDev &fine_trunk = img[IMG_FINE_TRUNK], &coarse_trunk = img[IMG_COARSE_TRUNK], &bend_only = img[IMG_BEND_ONLY];
     // the fine network's trunk once more, packed for the 16x16x32 kernel (nrnerf_net_x16.h): what the split-bender path's fine pass
     // runs when the call asks for no detail outputs
-    PassDev fine_trunk_x16, coarse_trunk_x16;
-    PassDev bend_x16;             // the bender + rigidity MLPs packed for the 16x16x32 stand-alone bender ("bf16" mode)
+    ImageDev &fine_trunk_x16 = img[IMG_FINE_TRUNK_X16], &coarse_trunk_x16 = img[IMG_COARSE_TRUNK_X16];
+    ImageDev &bend_x16 = img[IMG_BEND_X16];             // the bender + rigidity MLPs packed for the 16x16x32 stand-alone bender ("bf16" mode)
     // training (nrnerf_train.h): transposed trunk weights of both networks; train_ok: see training_eligible, fp32 or bf16
-    PassDev coarse_bwd, fine_bwd;
-    bool train_ok = false;
+    ImageDev &coarse_bwd = img[IMG_COARSE_BWD], &fine_bwd = img[IMG_FINE_BWD];
     // view-dependent head / time-conditioned baseline: bender-less forward images for trunk_fwd_train (with both branches of the head /
     // without the latent columns)
-    PassDev coarse_train, fine_train;
+    ImageDev &coarse_train = img[IMG_COARSE_TRAIN], &fine_train = img[IMG_FINE_TRAIN];
     // training of the ray bender (nrnerf_train_bend.h): its layers alone in fp32 (whatever the model's precision) and
     // their transposes; bend_train_ok: train_ok and a bender
-    PassDev bend_train_fwd, bend_train_bwd;
-    bool bend_train_ok = false;
-    // generic architecture (nrnerf_generic.h): layer programs instead of compiled plans; gen_* hold their packed images
-    bool generic = false;
-    int gen_compiled_bender = -1;   // >= 0: the bender has one of the compiled shapes (0: 5 x 64, 1: 7 x 64; latent 32, rigidity 3 x 32) and the
-                                    // stand-alone bender kernel (nrnerf_bend.h, image `bend_only`) takes the passes without detail outputs
-    GenArgs gen_bend_prog{}, gen_coarse_prog{}, gen_fine_prog{};
-    PassDev gen_bend, gen_coarse, gen_fine;
-    // the trunks of a generic model packed for the width-class 16x16x32 kernel (nrnerf_gx16.h): 16-bit modes, no view-dependent head
-    PassDev gx_coarse, gx_fine;
-    GxMeta gx_meta_coarse, gx_meta_fine;
+    ImageDev &bend_train_fwd = img[IMG_BEND_TRAIN_FWD], &bend_train_bwd = img[IMG_BEND_TRAIN_BWD];
+    // generic architecture (nrnerf_generic.h): layer programs (ImageDev::prog) instead of compiled plans
+    ImageDev &gen_bend = img[IMG_GEN_BEND], &gen_coarse = img[IMG_GEN_COARSE], &gen_fine;
+    // the trunks of a generic model packed for the width-class 16x16x32 kernel (nrnerf_gx16.h; ImageDev::gx): 16-bit modes
+    ImageDev &gx_coarse = img[IMG_GX_COARSE], &gx_fine = img[IMG_GX_FINE];
     // training of a generic model with a plain head (fp32 / bf16): the backward-data programs (transposed weights); the forward is
     // gen_coarse / gen_fine run with GenArgs::save set
-    bool gen_train_ok = false;
-    GenArgs gen_coarse_bwd_prog{}, gen_fine_bwd_prog{};
-    PassDev gen_coarse_bwd, gen_fine_bwd;
-    struct GenTrainNet { int W = 0, D = 0, dv = 0, draw_col = 0, in_w = 0, lat = 0; bool skip = false, views = false; } gen_tn[2];     // [coarse, fine]
-    bool gen_fine_is_coarse = false;
+    ImageDev &gen_coarse_bwd = img[IMG_GEN_COARSE_BWD], &gen_fine_bwd = img[IMG_GEN_FINE_BWD];
+    ImageDev &gx_coarse_bwd = img[IMG_GX_COARSE_BWD], &gx_fine_bwd = img[IMG_GX_FINE_BWD];          // backward-data programs of the width-class trunks (nrnerf_gx16_bwd.h), when gx16_trainable
     int64_t flat_floats = 0;      // length of the flat parameter vector nrnerf_model_update_device expects
-    PassDev gx_coarse_bwd, gx_fine_bwd;          // backward-data programs of the width-class trunks (nrnerf_gx16_bwd.h), when gx16_trainable
-    GxMeta gx_meta_coarse_bwd, gx_meta_fine_bwd;
     unsigned* adam_barrier = nullptr;   // two words of device memory: the grid barrier of nrnerf_adam_step (nrnerf_optim.hip)
     // profiling (guarded; the render path itself is otherwise read-only on the handle)
     mutable std::mutex prof_mu;
@@ -1078,12 +1139,12 @@ int pack_split(const nrnerf_model_desc& d, PackedPass& trunk, PackedPass& bend, 
 }
 
 // transposed trunk weights for the backward-data kernel; eligible models only (see nrnerf_model::train_ok)
-bool training_eligible(const nrnerf_model_desc& d, const nrnerf_model* m) {
+bool training_eligible(const nrnerf_model_desc& d, int arch_id) {
     // (with the view-dependent head: the directions are an input of the trunk's training kernels -- finite differences, the rays' own, or
     //  the exact Jacobian directions, whose tangent and its gradient come from nrnerf_bender_divergence_* (tangent / g_tangent))
     // (time-conditioned baseline, architecture 2: trained through the plain trunk's kernels, the latent columns of its two
     //  input layers as per-ray biases -- pack_pass, tcb_shift)
-    return (m->arch_id <= 2 || m->arch_id == 5) && d.precision != NRNERF_PREC_F16;
+    return (arch_id <= 2 || arch_id == 5) && d.precision != NRNERF_PREC_F16;
 }
 int tcb_shift_of(const nrnerf_mlp_desc& mlp) {      // latent columns of a time-conditioned trunk (0: plain trunk)
     return mlp.time_conditioned ? mlp.pts_linears[0].in_features - (3 + 6 * ArchDefault::L) : 0;
@@ -1101,60 +1162,6 @@ void pack_bwd(const nrnerf_model_desc& d, const nrnerf_mlp_desc& mlp, PackedPass
         else pack_pass_bwd<Shape16, ArchDefault>(mlp, d.precision, out, lay, ts);
     }
 }
-int upload_training(const nrnerf_model_desc& d, nrnerf_model* m, hipStream_t refresh_stream = nullptr, bool refresh = false,
-                    const FlatLayout* lay = nullptr) {
-    if (!training_eligible(d, m)) return NRNERF_OK;
-    PackedPass bc, bf;
-    pack_bwd(d, *d.coarse, bc, lay);
-    int rc = refresh ? refresh_pass(bc, m->coarse_bwd, refresh_stream) : upload_pass(bc, m->coarse_bwd);
-    if (rc == NRNERF_OK && d.fine) {
-        pack_bwd(d, *d.fine, bf, lay);
-        rc = refresh ? refresh_pass(bf, m->fine_bwd, refresh_stream) : upload_pass(bf, m->fine_bwd);
-    }
-    if (refresh && rc == NRNERF_OK && hipStreamSynchronize(refresh_stream) != hipSuccess) rc = NRNERF_ERR_HIP;   // host images die here
-    if (rc == NRNERF_OK && (m->views || d.coarse->time_conditioned)) {       // bender-less forward images: with the view-dependent head / without the latent columns
-        auto pack_train = [&](const nrnerf_mlp_desc& mlp, PackedPass& out) {
-            nrnerf_model_desc d2 = d;
-            d2.bender = nullptr;
-            const int ts = tcb_shift_of(mlp);
-            if (mlp.use_viewdirs) {             // trunk + both branches of the view-dependent head (trunk_fwd_train<.., VIEWS>)
-                if (d.precision == NRNERF_PREC_F32) pack_pass<ShapeF32, ArchDefault, false, true>(d2, mlp, d.precision, out, lay, ts);
-                else pack_pass<Shape16Fast, ArchDefault, false, true>(d2, mlp, d.precision, out, lay, ts);
-            } else if (d.precision == NRNERF_PREC_F32) pack_pass<ShapeF32, ArchDefault, false, false>(d2, mlp, d.precision, out, lay, ts);
-            else pack_pass<Shape16Fast, ArchDefault, false, false>(d2, mlp, d.precision, out, lay, ts);
-        };
-        PackedPass tc, tf;
-        pack_train(*d.coarse, tc);
-        rc = refresh ? refresh_pass(tc, m->coarse_train, refresh_stream) : upload_pass(tc, m->coarse_train);
-        if (rc == NRNERF_OK && d.fine) {
-            pack_train(*d.fine, tf);
-            rc = refresh ? refresh_pass(tf, m->fine_train, refresh_stream) : upload_pass(tf, m->fine_train);
-        }
-        if (refresh && rc == NRNERF_OK && hipStreamSynchronize(refresh_stream) != hipSuccess) rc = NRNERF_ERR_HIP;
-    }
-    const double mfma_flop = 2.0 * 32 * 32 * (d.precision == NRNERF_PREC_F32 ? 2 : 16);
-    m->coarse_bwd.mfma_flops_per_sample = bc.mfma_per_block * mfma_flop / 32.0;
-    m->fine_bwd.mfma_flops_per_sample = (d.fine ? bf.mfma_per_block : bc.mfma_per_block) * mfma_flop / 32.0;
-    m->train_ok = (rc == NRNERF_OK);
-    if (rc == NRNERF_OK && d.bender) {
-        PackedPass bfw, bbw;
-        nrnerf_model_desc d32 = d;
-        d32.precision = NRNERF_PREC_F32;
-        if (bender_arch(m->arch_id) == 0) {       // the bender-only plan does not depend on the trunk's width
-            pack_pass<ShapeF32, ArchDefault, true, false, false>(d32, *d.coarse, NRNERF_PREC_F32, bfw, lay);
-            pack_pass_bwd_bender<ArchDefault>(*d.bender, bbw, lay);
-        } else {
-            pack_pass<ShapeF32, ArchDeepBend, true, false, false>(d32, *d.coarse, NRNERF_PREC_F32, bfw, lay);
-            pack_pass_bwd_bender<ArchDeepBend>(*d.bender, bbw, lay);
-        }
-        rc = refresh ? refresh_pass(bfw, m->bend_train_fwd, refresh_stream) : upload_pass(bfw, m->bend_train_fwd);
-        if (rc == NRNERF_OK) rc = refresh ? refresh_pass(bbw, m->bend_train_bwd, refresh_stream) : upload_pass(bbw, m->bend_train_bwd);
-        if (refresh && rc == NRNERF_OK && hipStreamSynchronize(refresh_stream) != hipSuccess) rc = NRNERF_ERR_HIP;
-        m->bend_train_ok = (rc == NRNERF_OK);
-    }
-    return rc;
-}
-
 // does the bender have compiled architecture A's bender shape?  (check_arch_t's bender part)
 template <class A>
 bool bender_matches(const nrnerf_bender_desc& b) {
@@ -1395,7 +1402,7 @@ double gen_mfma_flops_per_sample(const GenArgs& g, bool f32) {
     for (int l = 0; l < g.n_layers; ++l) f += (double)g.layer[l].nt * (g.layer[l].ns0 + g.layer[l].ns1) * 2.0 * 32 * (f32 ? 8 : 16);
     return f;
 }
-// the compiled bender's training images for a generic handle (as pack_training's: the fp32 forward plan and the backward plan)
+// the training images of a bender of compiled shape cb, compiled or generic handle (the fp32 forward plan and the backward plan, whatever the model's precision)
 void gen_pack_bender_train(const nrnerf_model_desc& d, int cb, PackedPass& bfw, PackedPass& bbw, const FlatLayout* lay) {
     nrnerf_model_desc d32 = d;
     d32.precision = NRNERF_PREC_F32;
@@ -1407,219 +1414,191 @@ void gen_pack_bender_train(const nrnerf_model_desc& d, int cb, PackedPass& bfw, 
         pack_pass_bwd_bender<ArchDeepBend>(*d.bender, bbw, lay);
     }
 }
-int create_generic(const nrnerf_model_desc& d, const FlatLayout& lay, nrnerf_model** out) {
-    GenProgram gb, gc, gf;
-    int rc = gen_pack_all(d, &lay, gb, gc, gf);
-    if (rc != NRNERF_OK) return rc;
-    DeviceGuard guard(d.device);
-    if (!guard.ok) return NRNERF_ERR_HIP;
-    struct Owner {
-        nrnerf_model* m;
-        ~Owner() { if (m) nrnerf_model_destroy(m); }
-    } own{new (std::nothrow) nrnerf_model()};
-    nrnerf_model* m = own.m;
-    if (!m) return NRNERF_ERR_NOMEM;
-    m->generic = true;
-    m->device = d.device; m->precision = d.precision;
-    m->has_bend = d.bender != nullptr;
-    m->views = d.coarse->use_viewdirs != 0;
-    m->arch_id = -1; m->exact = 0;
-    m->needs_latents = m->has_bend || d.coarse->time_conditioned;
-    m->latent_size = d.bender ? d.bender->latent_size : gc.proto.lat;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, d.device) != hipSuccess) return NRNERF_ERR_HIP;
-    m->num_cus = prop.multiProcessorCount;
-    if (hipMalloc((void**)&m->adam_barrier, 2 * sizeof(unsigned)) != hipSuccess || hipMemset(m->adam_barrier, 0, 2 * sizeof(unsigned)) != hipSuccess) return NRNERF_ERR_NOMEM;
-    m->flat_floats = lay.total;
-    nrnerf_model_desc d2 = d;
-    d2.bender = nullptr;
-    if (d.bender) {
-        rc = upload_pass(gb.pk, m->gen_bend);
-        if (rc != NRNERF_OK) return rc;
-        m->gen_bend_prog = gb.proto;
-        m->gen_bend.algo_flops_per_sample = 2.0 * (algo_macs(d, *d.coarse) - algo_macs(d2, *d.coarse));
-        // the usual case -- an odd TRUNK with the reference's hard-coded bender (rnh:406-407): its compiled stand-alone kernel
-        const int cb = bender_matches<ArchDefault>(*d.bender) ? 0 : (bender_matches<ArchDeepBend>(*d.bender) ? 1 : -1);
-        if (cb >= 0) {
-            PackedPass pb;
-            auto go = [&](auto sh) {
-                using SH = decltype(sh);
-                if (cb == 0) pack_pass<SH, ArchDefault, true, false, false>(d, *d.coarse, d.precision, pb, &lay);
-                else pack_pass<SH, ArchDeepBend, true, false, false>(d, *d.coarse, d.precision, pb, &lay);
-            };
-            if (d.precision == NRNERF_PREC_F32) go(ShapeF32{});
-            else if (d.precision == NRNERF_PREC_BF16) go(Shape16Fast{});
-            else go(Shape16{});
-            rc = upload_pass(pb, m->bend_only);
-            if (rc != NRNERF_OK) return rc;
-            m->bend_only.algo_flops_per_sample = m->gen_bend.algo_flops_per_sample;
-            m->gen_compiled_bender = cb;
-            if (d.precision != NRNERF_PREC_F16) {    // ... and its training kernels (forward with saved activations, backward, divergence chains)
-                PackedPass bfw, bbw;
-                gen_pack_bender_train(d, cb, bfw, bbw, &lay);
-                rc = upload_pass(bfw, m->bend_train_fwd);
-                if (rc == NRNERF_OK) rc = upload_pass(bbw, m->bend_train_bwd);
-                if (rc != NRNERF_OK) return rc;
-                m->bend_train_ok = true;
-            }
-            if (bend_x16_eligible(d)) {              // "bf16" mode: the 16x16x32 stand-alone bender (nrnerf_bend_x16.h)
-                PackedPass pbx;
-                pack_bend_x16(d, pbx, &lay);
-                rc = upload_pass(pbx, m->bend_x16);
-                if (rc != NRNERF_OK) return rc;
-                m->bend_x16.algo_flops_per_sample = m->gen_bend.algo_flops_per_sample;
-                m->bend_x16.mfma_flops_per_sample = pbx.mfma_per_block * (2.0 * 16 * 16 * 32) / 16.0;
-            }
-        }
-    }
-    rc = upload_pass(gc.pk, m->gen_coarse);
-    if (rc != NRNERF_OK) return rc;
-    m->gen_coarse_prog = gc.proto;
-    m->gen_coarse.algo_flops_per_sample = 2.0 * algo_macs(d2, *d.coarse);
-    m->gen_coarse.output_ch = d.coarse->output_ch;
-    m->gen_coarse.mfma_flops_per_sample = gen_mfma_flops_per_sample(gc.proto, d.precision == NRNERF_PREC_F32);
-    m->coarse.output_ch = d.coarse->output_ch;
-    if (d.fine) {
-        rc = upload_pass(gf.pk, m->gen_fine);
-        if (rc != NRNERF_OK) return rc;
-        m->gen_fine_prog = gf.proto;
-        m->gen_fine.algo_flops_per_sample = 2.0 * algo_macs(d2, *d.fine);
-        m->gen_fine.output_ch = d.fine->output_ch;
-        m->gen_fine.mfma_flops_per_sample = gen_mfma_flops_per_sample(gf.proto, d.precision == NRNERF_PREC_F32);
-    } else {
-        m->gen_fine = m->gen_coarse; m->gen_fine_prog = m->gen_coarse_prog; m->gen_fine_is_coarse = true;
-    }
-    m->fine.output_ch = m->gen_fine.output_ch;
-    m->fine_is_coarse = !d.fine;
-    if (gen_trainable(d, *d.coarse) && (!d.fine || gen_trainable(d, *d.fine))) {
-        GenProgram bc, bf;
-        gen_pack_mlp_bwd(d, *d.coarse, bc, &lay);
-        rc = upload_pass(bc.pk, m->gen_coarse_bwd);
-        if (rc != NRNERF_OK) return rc;
-        m->gen_coarse_bwd_prog = bc.proto;
-        auto describe = [&](const nrnerf_mlp_desc& n) {
-            nrnerf_model::GenTrainNet t;
-            t.W = n.width; t.D = n.depth; t.skip = gen_skip(n) >= 0; t.views = n.use_viewdirs != 0;
-            t.dv = t.views ? 3 + 6 * d.multires_views : 0; t.draw_col = gen_draw_col(n);
-            t.in_w = n.time_conditioned ? n.pts_linears[0].in_features : 3 + 6 * d.multires; t.lat = t.in_w - (3 + 6 * d.multires);
-            return t;
-        };
-        m->gen_tn[0] = describe(*d.coarse);
-        if (d.fine) {
-            gen_pack_mlp_bwd(d, *d.fine, bf, &lay);
-            rc = upload_pass(bf.pk, m->gen_fine_bwd);
-            if (rc != NRNERF_OK) return rc;
-            m->gen_fine_bwd_prog = bf.proto;
-            m->gen_tn[1] = describe(*d.fine);
-        } else {
-            m->gen_tn[1] = m->gen_tn[0];
-        }
-        m->gen_train_ok = true;
-    }
-    m->exact = d.exact_viewdirs != 0 && m->has_bend && m->views;
-    if (m->exact && !(m->bend_train_ok && m->gen_train_ok)) return NRNERF_ERR_UNSUPPORTED;      // (needs bend_div_fwd and the per-sample-direction instantiation)
-    // the trunks also for the width-class x16 kernel: rendering passes that run on ready-made points (a bender in front), and the training
-    // forward of any such trunk (its points are always handed in)
-    if (gx16_eligible(d, *d.coarse) && (!d.fine || gx16_eligible(d, *d.fine))) {
-        PackedPass pgc, pgf;
-        pack_gx16(d, *d.coarse, pgc, m->gx_meta_coarse, &lay);
-        rc = upload_pass(pgc, m->gx_coarse);
-        if (rc != NRNERF_OK) return rc;
-        m->gx_coarse.algo_flops_per_sample = m->gen_coarse.algo_flops_per_sample;
-        m->gx_coarse.mfma_flops_per_sample = pgc.mfma_per_block * (2.0 * 16 * 16 * 32) / 16.0;
-        m->gx_coarse.output_ch = d.coarse->output_ch;
-        if (d.fine) {
-            pack_gx16(d, *d.fine, pgf, m->gx_meta_fine, &lay);
-            rc = upload_pass(pgf, m->gx_fine);
-            if (rc != NRNERF_OK) return rc;
-            m->gx_fine.algo_flops_per_sample = m->gen_fine.algo_flops_per_sample;
-            m->gx_fine.mfma_flops_per_sample = pgf.mfma_per_block * (2.0 * 16 * 16 * 32) / 16.0;
-            m->gx_fine.output_ch = d.fine->output_ch;
-        }
-        // ... and their backward-data programs (training: nrnerf_generic_trunk_backward on gx16_bwd_kernel)
-        if (m->gen_train_ok && gx16_trainable(d, *d.coarse) && (!d.fine || gx16_trainable(d, *d.fine))) {
-            PackedPass pbc, pbf;
-            pack_gx16_bwd(d, *d.coarse, pbc, m->gx_meta_coarse_bwd, &lay);
-            rc = upload_pass(pbc, m->gx_coarse_bwd);
-            if (rc != NRNERF_OK) return rc;
-            if (d.fine) {
-                pack_gx16_bwd(d, *d.fine, pbf, m->gx_meta_fine_bwd, &lay);
-                rc = upload_pass(pbf, m->gx_fine_bwd);
-                if (rc != NRNERF_OK) return rc;
-            }
-        }
-    }
-    own.m = nullptr;
-    *out = m;
-    return NRNERF_OK;
+// issued MFMA flops per sample of a packed image (padding included): a compiled plan issues mfma_per_block 32 x 32 x (2 | 16) MFMAs per block of 32
+// samples, the 16x16x32 kernels mfma_per_block 16 x 16 x 32 MFMAs per block of 16
+double mfma32_flops_per_sample(const PackedPass& pk, int precision) {
+    const double mfma_flop = 2.0 * 32 * 32 * (precision == NRNERF_PREC_F32 ? 2 : 16);
+    return pk.mfma_per_block * mfma_flop / 32.0;
 }
-int update_generic(nrnerf_model* m, const nrnerf_model_desc& d, hipStream_t stream) {
-    GenProgram gb, gc, gf;
-    int rc = gen_pack_all(d, nullptr, gb, gc, gf);
-    if (rc != NRNERF_OK) return rc == NRNERF_ERR_UNSUPPORTED ? NRNERF_ERR_INVALID : rc;
-    DeviceGuard guard(m->device);
-    if (!guard.ok) return NRNERF_ERR_HIP;
-    PackedPass pb;
-    if (d.bender && m->gen_compiled_bender >= 0) {
-        auto go = [&](auto sh) {
-            using SH = decltype(sh);
-            if (m->gen_compiled_bender == 0) pack_pass<SH, ArchDefault, true, false, false>(d, *d.coarse, d.precision, pb, nullptr);
-            else pack_pass<SH, ArchDeepBend, true, false, false>(d, *d.coarse, d.precision, pb, nullptr);
+double mfma16_flops_per_sample(const PackedPass& pk) { return pk.mfma_per_block * (2.0 * 16 * 16 * 32) / 16.0; }
+
+// The images of a model description, and what else the description makes of a handle (`t`).  Every eligibility decision and every
+// metadata formula of a handle lives here; no HIP call.  `lay` (create): the packers record where every element comes from in the flat
+// parameter vector (nrnerf_model_update_device); null for a refresh.  "No fine network" yields no IMG_FINE / IMG_GEN_FINE (the handle
+// resolves them to the coarse images).
+int pack_images(const nrnerf_model_desc& d, const FlatLayout* lay, ModelTraits& t, std::vector<Image>& out) {
+    t = ModelTraits{};
+    out.clear();
+    out.reserve(IMG_COUNT);            // (references to entries stay valid)
+    auto add = [&](ImageSlot s) -> Image& { out.emplace_back(s); return out.back(); };
+    if (d.fine && (d.fine->use_viewdirs != 0) != (d.coarse->use_viewdirs != 0)) return NRNERF_ERR_INVALID;
+    t.precision = d.precision;
+    t.has_bend = d.bender != nullptr;
+    t.views = d.coarse->use_viewdirs != 0;
+    t.exact = d.exact_viewdirs != 0 && t.has_bend && t.views;      // only meaningful with bender + view-dependent head
+    t.needs_latents = t.has_bend || d.coarse->time_conditioned;
+    t.fine_is_coarse = !d.fine;
+    const nrnerf_mlp_desc& fm = d.fine ? *d.fine : *d.coarse;       // the network of the fine pass
+    nrnerf_model_desc d2 = d;                                       // the model without its bender
+    d2.bender = nullptr;
+    const bool f32 = d.precision == NRNERF_PREC_F32;
+
+    int arch_f = 0;
+    int rc = pack_dispatch(d, *d.coarse, add(IMG_COARSE).pk, &t.arch_id, false, lay);
+    if (rc == NRNERF_OK && d.fine) {
+        rc = pack_dispatch(d, *d.fine, add(IMG_FINE).pk, &arch_f, false, lay);
+        if (rc == NRNERF_OK && arch_f != t.arch_id) rc = NRNERF_ERR_UNSUPPORTED;      // e.g. --netwidth_fine != --netwidth: generic below
+    }
+    // NRNERF_MODEL_FORCE_GENERIC: the generic kernel also for the compiled shapes (tests: the two routes against each other)
+    const bool force_generic = (d.flags & NRNERF_MODEL_FORCE_GENERIC) != 0;
+    if (rc == NRNERF_OK && force_generic && !(d.exact_viewdirs && d.bender && d.coarse->use_viewdirs)) rc = NRNERF_ERR_UNSUPPORTED;
+    if (rc != NRNERF_OK && rc != NRNERF_ERR_UNSUPPORTED) return rc;
+    t.generic = rc == NRNERF_ERR_UNSUPPORTED;
+
+    int cb = -1;                      // compiled shape of the bender (0: 5 x 64, 1: 7 x 64) when a stand-alone bender image exists
+    double bend_algo = 0;             // algorithmic flops per sample of the bender alone
+    if (!t.generic) {
+        // ---- compiled architecture: the fused passes ...
+        if (t.exact && t.arch_id > 1) return NRNERF_ERR_UNSUPPORTED;
+        t.latent_size = d.bender ? d.bender->latent_size : 0;
+        for (Image& im : out) {
+            const nrnerf_mlp_desc& mlp = im.slot == IMG_COARSE ? *d.coarse : *d.fine;
+            im.algo_flops = 2.0 * algo_macs(d, mlp);
+            im.mfma_flops = mfma32_flops_per_sample(im.pk, d.precision);
+            im.output_ch = mlp.output_ch;
+        }
+        // ... the split-bender path's (exact view directions need the bender's Jacobian: fused only; an architecture without a trunk-only
+        // plan simply has no split path) ...
+        Image ft(IMG_FINE_TRUNK), bo(IMG_BEND_ONLY), ct(IMG_COARSE_TRUNK);
+        if (t.has_bend && !t.exact && pack_split(d, ft.pk, bo.pk, &ct.pk, lay) == NRNERF_OK) {
+            t.split_ok = true;
+            cb = bender_arch(t.arch_id);
+            ft.algo_flops = 2.0 * algo_macs(d2, fm);
+            ft.output_ch = fm.output_ch;
+            ct.algo_flops = 2.0 * algo_macs(d2, *d.coarse);
+            ct.output_ch = d.coarse->output_ch;
+            bend_algo = bo.algo_flops = 2.0 * algo_macs(d, fm) - ft.algo_flops;
+            for (Image* im : {&ft, &bo, &ct}) im->mfma_flops = mfma32_flops_per_sample(im->pk, d.precision);
+            // ... with the trunks once more for the 16x16x32 kernel (the coarse network's: the coarse pass of the split path on it too)
+            for (const nrnerf_mlp_desc* mlp : {&fm, d.fine ? d.coarse : nullptr}) {
+                if (!mlp || !x16_eligible(d, *mlp)) continue;
+                Image& x = add(mlp == &fm ? IMG_FINE_TRUNK_X16 : IMG_COARSE_TRUNK_X16);
+                pack_x16(d, *mlp, x.pk, lay);
+                x.algo_flops = 2.0 * algo_macs(d2, *mlp);
+                x.mfma_flops = mfma16_flops_per_sample(x.pk);
+                x.output_ch = mlp->output_ch;
+            }
+            out.push_back(std::move(ft)); out.push_back(std::move(bo)); out.push_back(std::move(ct));
+        }
+        // ... and the training kernels' (nrnerf_train.h): transposed trunk weights, and -- view-dependent head / time-conditioned baseline --
+        // bender-less forward images with both branches of the head / without the latent columns
+        if (training_eligible(d, t.arch_id)) {
+            t.train_ok = true;
+            t.bend_train_ok = t.has_bend;
+            if (t.has_bend) cb = bender_arch(t.arch_id);
+            auto pack_train = [&](const nrnerf_mlp_desc& mlp, PackedPass& pk) {
+                const int ts = tcb_shift_of(mlp);
+                if (mlp.use_viewdirs) {             // trunk + both branches of the view-dependent head (trunk_fwd_train<.., VIEWS>)
+                    if (f32) pack_pass<ShapeF32, ArchDefault, false, true>(d2, mlp, d.precision, pk, lay, ts);
+                    else pack_pass<Shape16Fast, ArchDefault, false, true>(d2, mlp, d.precision, pk, lay, ts);
+                } else if (f32) pack_pass<ShapeF32, ArchDefault, false, false>(d2, mlp, d.precision, pk, lay, ts);
+                else pack_pass<Shape16Fast, ArchDefault, false, false>(d2, mlp, d.precision, pk, lay, ts);
+            };
+            for (const nrnerf_mlp_desc* mlp : {d.coarse, d.fine}) {
+                if (!mlp) continue;
+                Image& bw = add(mlp == d.coarse ? IMG_COARSE_BWD : IMG_FINE_BWD);
+                pack_bwd(d, *mlp, bw.pk, lay);
+                bw.mfma_flops = mfma32_flops_per_sample(bw.pk, d.precision);
+                if (t.views || d.coarse->time_conditioned) pack_train(*mlp, add(mlp == d.coarse ? IMG_COARSE_TRAIN : IMG_FINE_TRAIN).pk);
+            }
+        }
+    } else {
+        // ---- architecture outside the compiled set (nrnerf_generic.h): layer programs ...
+        out.clear();
+        t.arch_id = -1;
+        GenProgram gb, gc, gf;
+        rc = gen_pack_all(d, lay, gb, gc, gf);
+        if (rc != NRNERF_OK) return rc;
+        t.latent_size = d.bender ? d.bender->latent_size : gc.proto.lat;
+        auto program = [&](ImageSlot s, GenProgram& g, const nrnerf_mlp_desc* mlp) -> Image& {
+            Image& im = add(s);
+            im.pk = std::move(g.pk);
+            im.proto = g.proto;
+            if (mlp) {
+                im.algo_flops = 2.0 * algo_macs(d2, *mlp);
+                im.mfma_flops = gen_mfma_flops_per_sample(g.proto, f32);
+                im.output_ch = mlp->output_ch;
+            }
+            return im;
         };
-        if (!(m->gen_compiled_bender == 0 ? bender_matches<ArchDefault>(*d.bender) : bender_matches<ArchDeepBend>(*d.bender))) return NRNERF_ERR_INVALID;
-        if (d.precision == NRNERF_PREC_F32) go(ShapeF32{});
-        else if (d.precision == NRNERF_PREC_BF16) go(Shape16Fast{});
-        else go(Shape16{});
-        rc = refresh_pass(pb, m->bend_only, stream);
-        if (rc != NRNERF_OK) return rc;
-    }
-    PackedPass pbx;
-    if (d.bender && m->bend_x16.stream) {
-        pack_bend_x16(d, pbx);
-        rc = refresh_pass(pbx, m->bend_x16, stream);
-        if (rc != NRNERF_OK) return rc;
-    }
-    PackedPass tbf, tbb;
-    if (d.bender && m->bend_train_ok) {
-        gen_pack_bender_train(d, m->gen_compiled_bender, tbf, tbb, nullptr);
-        rc = refresh_pass(tbf, m->bend_train_fwd, stream);
-        if (rc == NRNERF_OK) rc = refresh_pass(tbb, m->bend_train_bwd, stream);
-        if (rc != NRNERF_OK) return rc;
-    }
-    if (d.bender) rc = refresh_pass(gb.pk, m->gen_bend, stream);         // (sizes differ for another architecture: NRNERF_ERR_INVALID)
-    if (rc == NRNERF_OK) rc = refresh_pass(gc.pk, m->gen_coarse, stream);
-    if (rc == NRNERF_OK && d.fine) rc = refresh_pass(gf.pk, m->gen_fine, stream);
-    GenProgram bwc, bwf;
-    if (rc == NRNERF_OK && m->gen_train_ok) {
-        gen_pack_mlp_bwd(d, *d.coarse, bwc, nullptr);
-        rc = refresh_pass(bwc.pk, m->gen_coarse_bwd, stream);
-        if (rc == NRNERF_OK && d.fine) {
-            gen_pack_mlp_bwd(d, *d.fine, bwf, nullptr);
-            rc = refresh_pass(bwf.pk, m->gen_fine_bwd, stream);
+        if (d.bender) {
+            bend_algo = program(IMG_GEN_BEND, gb, nullptr).algo_flops = 2.0 * (algo_macs(d, *d.coarse) - algo_macs(d2, *d.coarse));
+            // the usual case -- an odd TRUNK with the reference's hard-coded bender (rnh:406-407): its compiled stand-alone kernel ...
+            cb = t.gen_compiled_bender = bender_matches<ArchDefault>(*d.bender) ? 0 : (bender_matches<ArchDeepBend>(*d.bender) ? 1 : -1);
+            if (cb >= 0) {
+                Image& bo = add(IMG_BEND_ONLY);            // (mfma_flops stay 0: the profile records of a generic handle)
+                auto go = [&](auto sh) {
+                    using SH = decltype(sh);
+                    if (cb == 0) pack_pass<SH, ArchDefault, true, false, false>(d, *d.coarse, d.precision, bo.pk, lay);
+                    else pack_pass<SH, ArchDeepBend, true, false, false>(d, *d.coarse, d.precision, bo.pk, lay);
+                };
+                if (f32) go(ShapeF32{});
+                else if (d.precision == NRNERF_PREC_BF16) go(Shape16Fast{});
+                else go(Shape16{});
+                bo.algo_flops = bend_algo;
+                // ... and its training kernels (forward with saved activations, backward, divergence chains)
+                t.bend_train_ok = d.precision != NRNERF_PREC_F16;
+            }
+        }
+        program(IMG_GEN_COARSE, gc, d.coarse);
+        if (d.fine) program(IMG_GEN_FINE, gf, d.fine);
+        // ... their backward-data programs (training) ...
+        if (gen_trainable(d, *d.coarse) && (!d.fine || gen_trainable(d, *d.fine))) {
+            t.gen_train_ok = true;
+            for (const nrnerf_mlp_desc* mlp : {d.coarse, d.fine}) {
+                GenTrainNet& tn = t.gen_tn[mlp == d.coarse ? 0 : 1];
+                if (!mlp) { tn = t.gen_tn[0]; continue; }
+                GenProgram bw;
+                gen_pack_mlp_bwd(d, *mlp, bw, lay);
+                program(mlp == d.coarse ? IMG_GEN_COARSE_BWD : IMG_GEN_FINE_BWD, bw, nullptr);
+                tn.W = mlp->width; tn.D = mlp->depth; tn.skip = gen_skip(*mlp) >= 0; tn.views = mlp->use_viewdirs != 0;
+                tn.dv = tn.views ? 3 + 6 * d.multires_views : 0; tn.draw_col = gen_draw_col(*mlp);
+                tn.in_w = mlp->time_conditioned ? mlp->pts_linears[0].in_features : 3 + 6 * d.multires; tn.lat = tn.in_w - (3 + 6 * d.multires);
+            }
+        }
+        if (t.exact && !(t.bend_train_ok && t.gen_train_ok)) return NRNERF_ERR_UNSUPPORTED;      // (needs bend_div_fwd and the per-sample-direction instantiation)
+        // ... and the trunks also for the width-class x16 kernel: rendering passes that run on ready-made points (a bender in front), and the
+        // training forward of any such trunk (its points are always handed in); with their backward-data programs
+        // (training: nrnerf_generic_trunk_backward on gx16_bwd_kernel)
+        if (gx16_eligible(d, *d.coarse) && (!d.fine || gx16_eligible(d, *d.fine))) {
+            const bool trainable = t.gen_train_ok && gx16_trainable(d, *d.coarse) && (!d.fine || gx16_trainable(d, *d.fine));
+            for (const nrnerf_mlp_desc* mlp : {d.coarse, d.fine}) {
+                if (!mlp) continue;
+                Image& gx = add(mlp == d.coarse ? IMG_GX_COARSE : IMG_GX_FINE);
+                pack_gx16(d, *mlp, gx.pk, gx.gx, lay);
+                gx.algo_flops = 2.0 * algo_macs(d2, *mlp);
+                gx.mfma_flops = mfma16_flops_per_sample(gx.pk);
+                gx.output_ch = mlp->output_ch;
+                if (!trainable) continue;
+                Image& gxb = add(mlp == d.coarse ? IMG_GX_COARSE_BWD : IMG_GX_FINE_BWD);
+                pack_gx16_bwd(d, *mlp, gxb.pk, gxb.gx, lay);
+            }
         }
     }
-    PackedPass pgc, pgf;
-    if (rc == NRNERF_OK && m->gx_coarse.stream) {
-        GxMeta mc, mf;
-        pack_gx16(d, *d.coarse, pgc, mc);
-        rc = refresh_pass(pgc, m->gx_coarse, stream);
-        if (rc == NRNERF_OK && d.fine && m->gx_fine.stream) {
-            pack_gx16(d, *d.fine, pgf, mf);
-            rc = refresh_pass(pgf, m->gx_fine, stream);
-        }
+    // ---- either way, around a bender of a compiled shape: its training images (fp32 whatever the model's precision) and -- where the
+    //      stand-alone bender runs ("bf16" mode) -- its 16x16x32 image
+    if (t.bend_train_ok) {
+        Image& fwd = add(IMG_BEND_TRAIN_FWD);
+        Image& bwd = add(IMG_BEND_TRAIN_BWD);
+        gen_pack_bender_train(d, cb, fwd.pk, bwd.pk, lay);
     }
-    PackedPass pbc, pbf;
-    if (rc == NRNERF_OK && m->gx_coarse_bwd.stream) {
-        GxMeta mc, mf;
-        pack_gx16_bwd(d, *d.coarse, pbc, mc);
-        rc = refresh_pass(pbc, m->gx_coarse_bwd, stream);
-        if (rc == NRNERF_OK && d.fine && m->gx_fine_bwd.stream) {
-            pack_gx16_bwd(d, *d.fine, pbf, mf);
-            rc = refresh_pass(pbf, m->gx_fine_bwd, stream);
-        }
+    if ((t.split_ok || t.gen_compiled_bender >= 0) && bend_x16_eligible(d)) {
+        Image& bx = add(IMG_BEND_X16);
+        pack_bend_x16(d, bx.pk, lay);
+        bx.algo_flops = bend_algo;
+        bx.mfma_flops = mfma16_flops_per_sample(bx.pk);
     }
-    if (hipStreamSynchronize(stream) != hipSuccess && rc == NRNERF_OK) rc = NRNERF_ERR_HIP;      // the packed host images die with this call
-    return rc;
+    return NRNERF_OK;
 }
 
 }  // namespace
@@ -1743,19 +1722,10 @@ int nrnerf_model_create(const nrnerf_model_desc* desc, nrnerf_model** out) try {
     if (!out) return NRNERF_ERR_INVALID;
     *out = nullptr;
     if (!desc || desc->struct_size != sizeof(nrnerf_model_desc) || !desc->coarse) return NRNERF_ERR_INVALID;
-    PackedPass pc, pf;
-    int arch_id = 0, arch_f = 0;
     const FlatLayout lay = flat_layout(*desc);
-    if (desc->fine && (desc->fine->use_viewdirs != 0) != (desc->coarse->use_viewdirs != 0)) return NRNERF_ERR_INVALID;
-    int rc = pack_dispatch(*desc, *desc->coarse, pc, &arch_id, false, &lay);
-    if (rc == NRNERF_OK && desc->fine) {
-        rc = pack_dispatch(*desc, *desc->fine, pf, &arch_f, false, &lay);
-        if (rc == NRNERF_OK && arch_f != arch_id) rc = NRNERF_ERR_UNSUPPORTED;      // e.g. --netwidth_fine != --netwidth: generic below
-    }
-    // NRNERF_MODEL_FORCE_GENERIC: the generic kernel also for the compiled shapes (tests: the two routes against each other)
-    const bool force_generic = (desc->flags & NRNERF_MODEL_FORCE_GENERIC) != 0;
-    if (rc == NRNERF_OK && force_generic && !(desc->exact_viewdirs && desc->bender && desc->coarse->use_viewdirs)) rc = NRNERF_ERR_UNSUPPORTED;
-    if (rc == NRNERF_ERR_UNSUPPORTED) return create_generic(*desc, lay, out);
+    ModelTraits traits;
+    std::vector<Image> images;
+    int rc = pack_images(*desc, &lay, traits, images);
     if (rc != NRNERF_OK) return rc;
     DeviceGuard guard(desc->device);
     if (!guard.ok) return NRNERF_ERR_HIP;
@@ -1764,83 +1734,25 @@ int nrnerf_model_create(const nrnerf_model_desc* desc, nrnerf_model** out) try {
     struct Owner {
         nrnerf_model* m;
         ~Owner() { if (m) nrnerf_model_destroy(m); }
-    } own{new (std::nothrow) nrnerf_model()};
+    } own{new (std::nothrow) nrnerf_model(traits)};
     nrnerf_model* m = own.m;
     if (!m) return NRNERF_ERR_NOMEM;
     m->device = desc->device;
-    m->precision = desc->precision;
-    m->has_bend = desc->bender != nullptr;
-    m->views = desc->coarse->use_viewdirs != 0;
-    m->arch_id = arch_id;
-    m->exact = desc->exact_viewdirs != 0 && m->has_bend && m->views;     // only meaningful with bender + view-dependent head
-    if (m->exact && arch_id > 1) return NRNERF_ERR_UNSUPPORTED;
-    m->needs_latents = m->has_bend || desc->coarse->time_conditioned;
-    m->latent_size = desc->bender ? desc->bender->latent_size : 0;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, desc->device) != hipSuccess) return NRNERF_ERR_HIP;
     m->num_cus = prop.multiProcessorCount;
     if (hipMalloc((void**)&m->adam_barrier, 2 * sizeof(unsigned)) != hipSuccess || hipMemset(m->adam_barrier, 0, 2 * sizeof(unsigned)) != hipSuccess) return NRNERF_ERR_NOMEM;
     m->flat_floats = lay.total;
-    const double mfma_flop = 2.0 * 32 * 32 * (desc->precision == NRNERF_PREC_F32 ? 2 : 16);
-    rc = upload_pass(pc, m->coarse);
-    m->coarse.algo_flops_per_sample = 2.0 * algo_macs(*desc, *desc->coarse);
-    m->coarse.mfma_flops_per_sample = pc.mfma_per_block * mfma_flop / 32.0;
-    m->coarse.output_ch = desc->coarse->output_ch;
-    if (rc == NRNERF_OK && desc->fine) {
-        rc = upload_pass(pf, m->fine);
-        m->fine.algo_flops_per_sample = 2.0 * algo_macs(*desc, *desc->fine);
-        m->fine.mfma_flops_per_sample = pf.mfma_per_block * mfma_flop / 32.0;
-        m->fine.output_ch = desc->fine->output_ch;
-    } else {
-        m->fine = m->coarse;
-        m->fine_is_coarse = true;
+    for (const Image& im : images) {
+        ImageDev& dev = m->img[im.slot];
+        rc = upload_pass(im.pk, dev);
+        if (rc != NRNERF_OK) return rc;
+        dev.algo_flops_per_sample = im.algo_flops;
+        dev.mfma_flops_per_sample = im.mfma_flops;
+        dev.output_ch = im.output_ch;
+        dev.prog = im.proto;
+        dev.gx = im.gx;
     }
-    if (rc == NRNERF_OK && m->has_bend && !m->exact) {       // (exact view directions need the bender's Jacobian: fused only)
-        PackedPass pt, pb, pct;
-        if (pack_split(*desc, pt, pb, &pct, &lay) == NRNERF_OK) {
-            rc = upload_pass(pt, m->fine_trunk);
-            if (rc == NRNERF_OK) rc = upload_pass(pb, m->bend_only);
-            if (rc == NRNERF_OK) rc = upload_pass(pct, m->coarse_trunk);
-            m->coarse_trunk.mfma_flops_per_sample = pct.mfma_per_block * mfma_flop / 32.0;
-            m->coarse_trunk.output_ch = m->coarse.output_ch;
-            nrnerf_model_desc d2 = *desc;
-            d2.bender = nullptr;
-            m->fine_trunk.algo_flops_per_sample = 2.0 * algo_macs(d2, desc->fine ? *desc->fine : *desc->coarse);
-            m->fine_trunk.mfma_flops_per_sample = pt.mfma_per_block * mfma_flop / 32.0;
-            m->fine_trunk.output_ch = m->fine.output_ch;
-            m->coarse_trunk.algo_flops_per_sample = 2.0 * algo_macs(d2, *desc->coarse);
-            m->bend_only.algo_flops_per_sample = m->fine.algo_flops_per_sample - m->fine_trunk.algo_flops_per_sample;
-            m->bend_only.mfma_flops_per_sample = pb.mfma_per_block * mfma_flop / 32.0;
-            m->split_ok = (rc == NRNERF_OK);
-            const nrnerf_mlp_desc& fm = desc->fine ? *desc->fine : *desc->coarse;
-            if (rc == NRNERF_OK && x16_eligible(*desc, fm)) {
-                PackedPass px;
-                pack_x16(*desc, fm, px, &lay);
-                rc = upload_pass(px, m->fine_trunk_x16);
-                m->fine_trunk_x16.algo_flops_per_sample = m->fine_trunk.algo_flops_per_sample;
-                m->fine_trunk_x16.mfma_flops_per_sample = px.mfma_per_block * (2.0 * 16 * 16 * 32) / 16.0;
-                m->fine_trunk_x16.output_ch = m->fine.output_ch;
-            }
-            if (rc == NRNERF_OK && bend_x16_eligible(*desc)) {
-                PackedPass pbx;
-                pack_bend_x16(*desc, pbx, &lay);
-                rc = upload_pass(pbx, m->bend_x16);
-                m->bend_x16.algo_flops_per_sample = m->bend_only.algo_flops_per_sample;
-                m->bend_x16.mfma_flops_per_sample = pbx.mfma_per_block * (2.0 * 16 * 16 * 32) / 16.0;
-            }
-            // the coarse network's trunk in the same packing: the coarse pass of the split path on the 16x16x32 kernel too
-            if (rc == NRNERF_OK && desc->fine && x16_eligible(*desc, *desc->coarse)) {
-                PackedPass pxc;
-                pack_x16(*desc, *desc->coarse, pxc, &lay);
-                rc = upload_pass(pxc, m->coarse_trunk_x16);
-                m->coarse_trunk_x16.algo_flops_per_sample = m->coarse_trunk.algo_flops_per_sample;
-                m->coarse_trunk_x16.mfma_flops_per_sample = pxc.mfma_per_block * (2.0 * 16 * 16 * 32) / 16.0;
-                m->coarse_trunk_x16.output_ch = m->coarse.output_ch;
-            }
-        }
-    }
-    if (rc == NRNERF_OK) rc = upload_training(*desc, m, nullptr, false, &lay);
-    if (rc != NRNERF_OK) return rc;
     own.m = nullptr;
     *out = m;
     return NRNERF_OK;
@@ -1848,50 +1760,24 @@ int nrnerf_model_create(const nrnerf_model_desc* desc, nrnerf_model** out) try {
 
 int nrnerf_model_update(nrnerf_model* m, const nrnerf_model_desc* desc, void* hip_stream) try {
     if (!m || !desc || desc->struct_size != sizeof(nrnerf_model_desc) || !desc->coarse) return NRNERF_ERR_INVALID;
-    if (desc->device != m->device || desc->precision != m->precision || (desc->bender != nullptr) != (m->has_bend != 0) ||
-        (desc->coarse->use_viewdirs != 0) != (m->views != 0) || (desc->fine != nullptr) == m->fine_is_coarse ||
-        ((desc->exact_viewdirs != 0 && m->has_bend && m->views) != (m->exact != 0)))
-        return NRNERF_ERR_INVALID;                     // a different model: create a new handle instead
-    if (m->generic) return update_generic(m, *desc, (hipStream_t)hip_stream);
-    PackedPass pc, pf;
-    int arch_id = 0, arch_f = 0;
-    int rc = pack_dispatch(*desc, *desc->coarse, pc, &arch_id);
+    if (desc->device != m->device) return NRNERF_ERR_INVALID;
+    ModelTraits traits;
+    std::vector<Image> images;
+    int rc = pack_images(*desc, nullptr, traits, images);
+    if (rc == NRNERF_ERR_UNSUPPORTED) return NRNERF_ERR_INVALID;
     if (rc != NRNERF_OK) return rc;
-    if (desc->fine) {
-        rc = pack_dispatch(*desc, *desc->fine, pf, &arch_f);
-        if (rc != NRNERF_OK) return rc;
-    }
-    if (arch_id != m->arch_id || (desc->fine && arch_f != m->arch_id)) return NRNERF_ERR_INVALID;
+    // a different model (architecture, precision, shape: other traits or another set of images): create a new handle instead
+    size_t n_resident = 0;
+    for (const ImageDev& dev : m->img) n_resident += dev.stream != nullptr;
+    if (!same_traits(traits, *m) || images.size() != n_resident) return NRNERF_ERR_INVALID;
+    for (const Image& im : images)
+        if (!m->img[im.slot].stream) return NRNERF_ERR_INVALID;
     DeviceGuard guard(m->device);
     if (!guard.ok) return NRNERF_ERR_HIP;
     hipStream_t stream = (hipStream_t)hip_stream;
-    rc = refresh_pass(pc, m->coarse, stream);
-    if (rc == NRNERF_OK && desc->fine) rc = refresh_pass(pf, m->fine, stream);
-    PackedPass pt, pb, pct;
-    if (rc == NRNERF_OK && m->split_ok) {
-        rc = pack_split(*desc, pt, pb, &pct);
-        if (rc == NRNERF_OK) rc = refresh_pass(pt, m->fine_trunk, stream);
-        if (rc == NRNERF_OK) rc = refresh_pass(pb, m->bend_only, stream);
-        if (rc == NRNERF_OK) rc = refresh_pass(pct, m->coarse_trunk, stream);
-    }
-    PackedPass px;
-    if (rc == NRNERF_OK && m->fine_trunk_x16.stream) {
-        pack_x16(*desc, desc->fine ? *desc->fine : *desc->coarse, px);
-        rc = refresh_pass(px, m->fine_trunk_x16, stream);
-    }
-    PackedPass pbx;
-    if (rc == NRNERF_OK && m->bend_x16.stream) {
-        pack_bend_x16(*desc, pbx);
-        rc = refresh_pass(pbx, m->bend_x16, stream);
-    }
-    PackedPass pxc;
-    if (rc == NRNERF_OK && m->coarse_trunk_x16.stream) {
-        pack_x16(*desc, *desc->coarse, pxc);
-        rc = refresh_pass(pxc, m->coarse_trunk_x16, stream);
-    }
+    for (size_t i = 0; i < images.size() && rc == NRNERF_OK; ++i) rc = refresh_pass(images[i].pk, m->img[images[i].slot], stream);
     // the packed host images die with this call: wait until the copies have consumed them
     if (hipStreamSynchronize(stream) != hipSuccess && rc == NRNERF_OK) rc = NRNERF_ERR_HIP;
-    if (rc == NRNERF_OK && m->train_ok) rc = upload_training(*desc, m, stream, /*refresh=*/true);
     return rc;
 } NRN_CATCH
 
@@ -1914,11 +1800,8 @@ int device_of(const void* ptr, int& dev);
 // called per full batch of REPACK_MAX_SEGMENTS and once for the last (possibly empty) one
 template <class EMIT>
 int repack_batches(nrnerf_model* m, const float* flat_params, EMIT&& emit) {
-    PassDev* passes[] = {&m->coarse, m->fine_is_coarse ? nullptr : &m->fine, &m->fine_trunk, &m->coarse_trunk, &m->bend_only, &m->fine_trunk_x16, &m->coarse_trunk_x16, &m->bend_x16,
-                         &m->coarse_bwd, &m->fine_bwd, &m->bend_train_fwd, &m->bend_train_bwd, &m->coarse_train, &m->fine_train,
-                         &m->gen_bend, &m->gen_coarse, m->gen_fine_is_coarse ? nullptr : &m->gen_fine, &m->gx_coarse, &m->gx_fine, &m->gen_coarse_bwd, &m->gen_fine_bwd, &m->gx_coarse_bwd, &m->gx_fine_bwd};
-    for (PassDev* p : passes)
-        if (p && p->stream && !p->src) return NRNERF_ERR_UNSUPPORTED;          // (before anything is launched)
+    for (const ImageDev& p : m->img)
+        if (p.stream && !p.src) return NRNERF_ERR_UNSUPPORTED;          // (before anything is launched)
     RepackBatchArgs b{};
     b.flat = flat_params;
     auto add = [&](const int32_t* src, const uint8_t* fmt, void* dst, long long n) -> bool {
@@ -1933,9 +1816,9 @@ int repack_batches(nrnerf_model* m, const float* flat_params, EMIT&& emit) {
         b.block0[k + 1] = b.block0[k] + (unsigned)((n + 255) / 256);
         return true;
     };
-    for (PassDev* p : passes) {
-        if (!p || !p->stream) continue;
-        if (!add(p->src, p->fmt, p->stream, (long long)p->n_elems) || !add(p->bias_src, nullptr, p->bias, (long long)p->bias_floats)) return NRNERF_ERR_HIP;
+    for (const ImageDev& p : m->img) {
+        if (!p.stream) continue;
+        if (!add(p.src, p.fmt, p.stream, (long long)p.n_elems) || !add(p.bias_src, nullptr, p.bias, (long long)p.bias_floats)) return NRNERF_ERR_HIP;
     }
     return emit(b, true) ? NRNERF_OK : NRNERF_ERR_HIP;
 }
@@ -2080,52 +1963,15 @@ void nrnerf_model_destroy(nrnerf_model* m) {
     (void)hipGetDevice(&prev);
     (void)hipSetDevice(m->device);
     for (auto& e : m->prof_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    if (!m->fine_is_coarse) free_pass(m->fine);
-    free_pass(m->coarse);
-    free_pass(m->fine_trunk);
-    free_pass(m->fine_trunk_x16);
-    free_pass(m->coarse_trunk_x16);
-    free_pass(m->bend_x16);
-    free_pass(m->gx_coarse);
-    free_pass(m->gx_fine);
-    free_pass(m->gx_coarse_bwd);
-    free_pass(m->gx_fine_bwd);
-    free_pass(m->gen_coarse_bwd);
-    free_pass(m->gen_fine_bwd);
-    free_pass(m->coarse_trunk);
-    free_pass(m->bend_only);
-    free_pass(m->coarse_bwd);
-    free_pass(m->fine_bwd);
-    free_pass(m->bend_train_fwd);
-    free_pass(m->bend_train_bwd);
-    free_pass(m->coarse_train);
-    free_pass(m->fine_train);
-    free_pass(m->gen_bend);
-    if (!m->gen_fine_is_coarse) free_pass(m->gen_fine);
-    free_pass(m->gen_coarse);
+    for (ImageDev& im : m->img) free_pass(im);
     if (m->adam_barrier) (void)hipFree(m->adam_barrier);
     (void)hipSetDevice(prev);
     delete m;
 }
 
-// work counters of the 16x16x32 stand-alone bender (BendArgs::work_counter): two launches per call, up to 512 counters each, 64 bytes apart
-constexpr int BEND_COUNTERS_PER_LAUNCH = 512;
-// ... and behind them one counter per 16x16x32 trunk launch (NetArgs::work_counter), 64 bytes apart
-constexpr size_t BEND_COUNTER_BYTES = (size_t)2 * BEND_COUNTERS_PER_LAUNCH * 64 + 256;
 size_t nrnerf_workspace_bytes(const nrnerf_model* model, int32_t n_rays, int32_t n_samples, int32_t n_importance) {
     if (n_rays <= 0 || n_samples <= 0 || n_importance < 0) return 0;
-    const size_t N = (size_t)n_rays, S = (size_t)n_samples, SF = S + (size_t)n_importance;
-    size_t b = align_up(N * S * 4 * sizeof(float), 256);
-    if (n_importance > 0) b += align_up(N * SF * sizeof(float), 256) + align_up(N * SF * 4 * sizeof(float), 256);
-    b += align_up(N * SF * 4 * sizeof(float), 256);      // bent point + rigidity of the final pass (surface reduction, split-bender path)
-    b += align_up(N * S * sizeof(float), 256);           // jittered coarse depths (perturb > 0)
-    if (n_importance > 0) {                              // split-bender path: coarse bent points, depths + rows of the new samples
-        b += align_up(N * S * 4 * sizeof(float), 256);
-        b += align_up(N * (SF - S) * sizeof(float), 256) + align_up(N * (SF - S), 256);
-    }
-    if (model && model->generic && model->exact) b += align_up(N * SF * 3 * sizeof(float), 256);      // per-sample Jacobian directions of a pass
-    b += BEND_COUNTER_BYTES;                             // work counters of the stand-alone bender launches (BendArgs::work_counter)
-    return b;
+    return WorkspaceLayout(n_rays, n_samples, n_importance, model && model->generic && model->exact).total;
 }
 
 int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_stream) try {
@@ -2136,7 +1982,7 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
     if (!a->rays || a->ray_stride < 8 || !a->rgb_map || !a->disp_map || !a->acc_map) return NRNERF_ERR_INVALID;
     if (m->needs_latents && (!a->latents || a->latent_stride < 0)) return NRNERF_ERR_INVALID;
     if (m->views && (!m->has_bend || m->exact) && a->ray_stride < 11) return NRNERF_ERR_INVALID;   // needs the unit view directions
-    const size_t need = nrnerf_workspace_bytes(m, a->n_rays, a->n_samples, a->n_importance);
+    const size_t need = nrnerf_workspace_bytes(m, a->n_rays, a->n_samples, a->n_importance);      // (= WorkspaceLayout::total below)
     if (!a->workspace || a->workspace_bytes < need || ((uintptr_t)a->workspace & 255)) return NRNERF_ERR_WORKSPACE;
     hipStream_t stream = (hipStream_t)hip_stream;
     const int N = a->n_rays, S = a->n_samples, I = a->n_importance, SF = S + I;
@@ -2144,20 +1990,14 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
     DeviceGuard guard(m->device);
     if (!guard.ok) return NRNERF_ERR_HIP;
 
-    char* ws = (char*)a->workspace;
-    float* raw_c = (float*)ws;
-    ws += align_up((size_t)N * S * 4 * sizeof(float), 256);
-    float* z_fine = nullptr; float* raw_f = nullptr;
-    if (I > 0) {
-        z_fine = (float*)ws; ws += align_up((size_t)N * SF * sizeof(float), 256);
-        raw_f = (float*)ws; ws += align_up((size_t)N * SF * 4 * sizeof(float), 256);
-    }
+    const WorkspaceLayout lay(N, S, I, m->generic && m->exact);
+    void* const ws = a->workspace;
+    float* const raw_c = lay.at<float>(ws, lay.raw_c);
+    float* const z_fine = lay.at<float>(ws, lay.z_fine, I > 0);
+    float* const raw_f = lay.at<float>(ws, lay.raw_f, I > 0);
     const bool surface = a->surface_pts || a->surface_rigidity || a->median_index;
-    float* bent4 = (float*)ws;
-    float* const bent4_ws = bent4;       // (the slot itself: `bent4` is nulled below when the compiled path does not need it)
-    ws += align_up((size_t)N * SF * 4 * sizeof(float), 256);
-    float* z_coarse = (float*)ws;
-    ws += align_up((size_t)N * S * sizeof(float), 256);
+    float* const bent4_ws = lay.at<float>(ws, lay.bent4);       // (the slot itself: `bent4` is null when the compiled path does not need it)
+    float* const z_coarse = lay.at<float>(ws, lay.z_coarse);
     // Split-bender path: bender, no view-dependent head, a fine pass, no per-sample detail outputs (those are written by
     // the fused kernels).  NRNERF_RENDER_FUSED_FINE_BENDER keeps the fused fine pass (A/B and bit-identity tests).
     auto any_detail = [](const nrnerf_sample_outputs& o) {
@@ -2169,34 +2009,27 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
     // (8-bit ranks among the merged depths: beyond 256 samples per ray the fused-bender fine pass renders)
     const bool split = m->split_ok && I > 0 && !a->detailed_output && !any_detail(a->coarse) && !any_detail(a->fine) && !force_fused &&
                        (long long)N * ((imax(S, I) + 31) / 32) < (1ll << 31) && SF <= 256;
-    float* bent_c = nullptr; float* z_new = nullptr; uint8_t* rank_new = nullptr;
-    if (I > 0) {
-        bent_c = (float*)ws; ws += align_up((size_t)N * S * 4 * sizeof(float), 256);
-        z_new = (float*)ws; ws += align_up((size_t)N * I * sizeof(float), 256);
-        rank_new = (uint8_t*)ws; ws += align_up((size_t)N * I, 256);
-    }
-    float* const jdirs = (m->generic && m->exact) ? (float*)ws : nullptr;      // [N, S + I | S, 3]: exact Jacobian directions of the pass in flight
-    if (m->generic && m->exact) ws += align_up((size_t)N * SF * 3 * sizeof(float), 256);
+    float* const bent4 = (surface || split) ? bent4_ws : nullptr;
+    float* const bent_c = lay.at<float>(ws, lay.bent_c, I > 0);
+    float* const z_new = lay.at<float>(ws, lay.z_new, I > 0);
+    uint8_t* const rank_new = lay.at<uint8_t>(ws, lay.rank_new, I > 0);
+    float* const jdirs = lay.at<float>(ws, lay.jdirs, m->generic && m->exact);      // [N, S + I | S, 3]: exact Jacobian directions of the pass in flight
     // one counter per stand-alone bender launch of the call (64 bytes apart), zeroed by ONE memset node ahead of the first launch
-    unsigned* const bend_counters = (unsigned*)ws;
+    unsigned* const bend_counters = lay.at<unsigned>(ws, lay.counters);
     bool counters_zeroed = false;
+    auto zeroed_counters = [&]() -> unsigned* {              // (the block, zeroed once per call; nullptr: the kernels' fixed shares)
+        if (!counters_zeroed && hipMemsetAsync(bend_counters, 0, BEND_COUNTER_BYTES, stream) != hipSuccess) return nullptr;
+        counters_zeroed = true;
+        return bend_counters;
+    };
     auto bend_counter = [&](int which) -> unsigned* {      // (per launch: one counter per pair of co-resident workgroups, 64 bytes apart)
-        if (m->num_cus > BEND_COUNTERS_PER_LAUNCH) return nullptr;                                  // (nullptr: the kernel's fixed shares)
-        if (!counters_zeroed) {
-            if (hipMemsetAsync(bend_counters, 0, BEND_COUNTER_BYTES, stream) != hipSuccess) return nullptr;
-            counters_zeroed = true;
-        }
-        return bend_counters + (size_t)16 * BEND_COUNTERS_PER_LAUNCH * which;
+        unsigned* const c = m->num_cus > BEND_COUNTERS_PER_LAUNCH ? nullptr : zeroed_counters();
+        return c ? c + (size_t)16 * BEND_COUNTERS_PER_LAUNCH * which : nullptr;
     };
-    auto trunk_counter = [&](int which) -> unsigned* {     // (0: coarse pass, 1: fine pass; nullptr: fixed shares)
-        if (a->flags & NRNERF_RENDER_FIXED_SHARES) return nullptr;
-        if (!counters_zeroed) {
-            if (hipMemsetAsync(bend_counters, 0, BEND_COUNTER_BYTES, stream) != hipSuccess) return nullptr;
-            counters_zeroed = true;
-        }
-        return bend_counters + (size_t)16 * BEND_COUNTERS_PER_LAUNCH * 2 + 16 * which;
+    auto trunk_counter = [&](int which) -> unsigned* {     // (0: coarse pass, 1: fine pass)
+        unsigned* const c = (a->flags & NRNERF_RENDER_FIXED_SHARES) ? nullptr : zeroed_counters();
+        return c ? c + (size_t)16 * BEND_COUNTERS_PER_LAUNCH * 2 + 16 * which : nullptr;
     };
-    if (!surface && !split) bent4 = nullptr;
     if ((a->u_fine || a->noise_fine) && I == 0) return NRNERF_ERR_INVALID;
 
     Knobs kn{};
@@ -2232,18 +2065,6 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
     // asks for the 32x32x16 one (NRNERF_RENDER_BENDER_32X32: the bit-identity tests against the fused-bender kernels)
     const bool bend_x16 = m->bend_x16.stream && !(a->flags & (NRNERF_RENDER_BENDER_32X32 | NRNERF_RENDER_NO_X16));
     if (bend_x16 && !(a->flags & NRNERF_RENDER_FIXED_SHARES)) (void)bend_counter(0);       // (the memset node ahead of every timed launch)
-    auto run_bender = [&](BendArgs& b, int slot, int n_samples) -> hipError_t {
-        if (bend_x16) {
-            b.wstream = m->bend_x16.stream; b.bias = m->bend_x16.bias;
-            b.work_counter = (a->flags & NRNERF_RENDER_FIXED_SHARES) ? nullptr : bend_counter(slot == 5 ? 0 : 1);
-            return timed(slot, "bend_kernel_x16", (double)N * n_samples * m->bend_x16.algo_flops_per_sample, (double)N * n_samples * m->bend_x16.mfma_flops_per_sample,
-                         [&] { return launch_bend_x16(bender_arch(m->arch_id), b, m->num_cus, stream); });
-        }
-        b.wstream = m->bend_only.stream; b.bias = m->bend_only.bias;
-        return timed(slot, "bend_kernel", (double)N * n_samples * m->bend_only.algo_flops_per_sample, (double)N * n_samples * m->bend_only.mfma_flops_per_sample,
-                     [&] { return launch_bend(m->precision, bender_arch(m->arch_id), b, m->num_cus, stream); });
-    };
-
     // ---- stratified jitter of the coarse depths (perturb > 0): both coarse kernels then read explicit depths
     const float* zc = nullptr;
     if (a->u_coarse) {
@@ -2251,6 +2072,50 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
         if (launch_zjitter(ja, stream) != hipSuccess) return NRNERF_ERR_HIP;
         zc = z_coarse;
     }
+
+    // `n_per_ray` samples of every ray at depths zv (null: the coarse spacing) through the bender, bent points to out4 [N, out_stride, 4] -- at
+    // row rank[.] of the ray when `rank` is given, else in order.  Profile slot 5 / 4: the coarse / fine pass.  `dynamic_shares`: the 16x16x32
+    // kernel hands its blocks out through a work counter (unless NRNERF_RENDER_FIXED_SHARES)
+    auto run_bender = [&](int slot, const float* zv, const uint8_t* rank, int n_per_ray, int out_stride, float* out4, bool dynamic_shares) -> hipError_t {
+        BendArgs b{};
+        b.rays = a->rays; b.ray_stride = a->ray_stride; b.latents = a->latents; b.lat_stride = a->latent_stride;
+        b.z = zv; b.lindisp = a->lindisp; b.rank = rank; b.n_rays = N; b.n_per_ray = n_per_ray; b.out_stride = out_stride;
+        b.bent4 = out4; b.knobs = kn;
+        const int arch = bender_arch_of(m);
+        const ImageDev& im = bend_x16 ? m->bend_x16 : m->bend_only;
+        b.wstream = im.stream; b.bias = im.bias;
+        const double samples = (double)N * n_per_ray;
+        if (bend_x16) {
+            b.work_counter = (dynamic_shares && !(a->flags & NRNERF_RENDER_FIXED_SHARES)) ? bend_counter(slot == 5 ? 0 : 1) : nullptr;
+            return timed(slot, "bend_kernel_x16", samples * im.algo_flops_per_sample, samples * im.mfma_flops_per_sample,
+                         [&] { return launch_bend_x16(arch, b, m->num_cus, stream); });
+        }
+        return timed(slot, "bend_kernel", samples * im.algo_flops_per_sample, samples * im.mfma_flops_per_sample,
+                     [&] { return launch_bend(m->precision, arch, b, m->num_cus, stream); });
+    };
+    // The compositing arguments of a pass.  `final`: the pass whose maps are the call's outputs (the only pass, or the fine one) -- raw4 null
+    // when they are the epilogue of the pass' network kernel; else the coarse pass of a hierarchical render: rgb0 / disp0 / acc0, sample_pdf and
+    // the merged depths of the fine pass
+    auto composite_args = [&](bool final, const float* raw4) {
+        const bool fine = final && I > 0;
+        const nrnerf_sample_outputs& so = fine ? a->fine : a->coarse;
+        CompositeArgs c{};
+        c.rays = a->rays; c.ray_stride = a->ray_stride;
+        c.raw4 = raw4; c.z = fine ? z_fine : zc; c.n_rays = N; c.S = fine ? SF : S; c.n_importance = final ? 0 : I;
+        c.lindisp = a->lindisp; c.white_bkgd = a->white_bkgd; c.noise = fine ? a->noise_fine : a->noise_coarse;
+        c.vis = so.visibility_weights; c.alpha = so.opacity_alpha;
+        if (final) {
+            c.rgb = a->rgb_map; c.disp = a->disp_map; c.acc = a->acc_map; c.z_user = a->z_vals;
+            if (surface) { c.bent4 = bent4_ws; c.surf_pts = a->surface_pts; c.surf_rig = a->surface_rigidity; c.med_idx = a->median_index; }
+        } else {
+            // rgb0/disp0/acc0 are optional for the caller but the kernel always writes them: park them in raw_f
+            // (not yet written) when the caller passed NULL.
+            c.u = a->u_fine;
+            c.rgb = a->rgb0 ? a->rgb0 : raw_f; c.disp = a->disp0 ? a->disp0 : raw_f + (size_t)N * 3; c.acc = a->acc0 ? a->acc0 : raw_f + (size_t)N * 4;
+            c.z_std = a->z_std; c.z_out = z_fine;
+        }
+        return c;
+    };
 
     if (m->generic) {
         // ---- architecture outside the compiled set (nrnerf_generic.h): per pass the bender over all samples of the pass (no
@@ -2260,23 +2125,11 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
         auto bender_pass = [&](const float* zv, int nS, float* out4, const nrnerf_sample_outputs& so, int slot) -> hipError_t {
             if (m->gen_compiled_bender >= 0 && !any_detail(so) && (long long)N * ((nS + 31) / 32) < (1ll << 31)) {
                 // the reference's own bender shape: the compiled stand-alone kernel (weights resident in LDS), all nS samples of a ray
-                BendArgs b{};
-                b.rays = a->rays; b.ray_stride = a->ray_stride; b.latents = a->latents; b.lat_stride = a->latent_stride;
-                b.z = zv; b.lindisp = a->lindisp; b.rank = nullptr; b.n_rays = N; b.n_per_ray = nS; b.out_stride = nS;
-                b.bent4 = out4; b.knobs = kn;
-                if (bend_x16) {
-                    b.wstream = m->bend_x16.stream; b.bias = m->bend_x16.bias;
-                    // (fixed shares here: with all nS samples of a ray in one launch the counters measured SLOWER -- width 192: 1.72 -> 1.82 ms
-                    //  per fine pass, profiles/r06_dynamic_shares_ab.txt -- where the split path's launches gain 8 %)
-                    b.work_counter = nullptr;
-                    return timed(slot, "bend_kernel_x16", (double)N * nS * m->bend_x16.algo_flops_per_sample, (double)N * nS * m->bend_x16.mfma_flops_per_sample,
-                                 [&] { return launch_bend_x16(m->gen_compiled_bender, b, m->num_cus, stream); });
-                }
-                b.wstream = m->bend_only.stream; b.bias = m->bend_only.bias;
-                return timed(slot, "bend_kernel", (double)N * nS * m->bend_only.algo_flops_per_sample, 0,
-                             [&] { return launch_bend(m->precision, m->gen_compiled_bender, b, m->num_cus, stream); });
+                // (fixed shares here: with all nS samples of a ray in one launch the counters measured SLOWER -- width 192: 1.72 -> 1.82 ms
+                //  per fine pass, profiles/r06_dynamic_shares_ab.txt -- where the split path's launches gain 8 %)
+                return run_bender(slot, zv, nullptr, nS, nS, out4, /*dynamic_shares=*/false);
             }
-            GenArgs g = m->gen_bend_prog;
+            GenArgs g = m->gen_bend.prog;
             g.rays = a->rays; g.ray_stride = a->ray_stride; g.latents = a->latents; g.lat_stride = a->latent_stride;
             g.z = zv; g.lindisp = a->lindisp; g.n_rays = N; g.S = nS;
             g.wstream = m->gen_bend.stream; g.bias = m->gen_bend.bias;
@@ -2289,10 +2142,8 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
                                 float* bent_out, const nrnerf_sample_outputs& so, int slot, const CompositeArgs* fuse = nullptr,
                                 bool* fused = nullptr) -> hipError_t {
             // the trunk on the width-class 16x16x32 kernel (nrnerf_gx16.h) when the pass runs on ready-made points and wants no detail outputs
-            const PassDev& gx = (&pd == &m->gen_coarse) ? m->gx_coarse : m->gx_fine;
-            const GxMeta& gm = (&pd == &m->gen_coarse) ? m->gx_meta_coarse : m->gx_meta_fine;
-            const PassDev& gxu = (m->gen_fine_is_coarse && &pd == &m->gen_fine) ? m->gx_coarse : gx;      // (one network for both passes)
-            const GxMeta& gmu = (m->gen_fine_is_coarse && &pd == &m->gen_fine) ? m->gx_meta_coarse : gm;
+            const ImageDev& gxu = (&pd == &m->gen_coarse) ? m->gx_coarse : m->gx_fine;      // (one network for both passes: gen_fine IS gen_coarse)
+            const GxMeta& gmu = gxu.gx;
             if (m->exact) {
                 // exact Jacobian view directions (rnh:291-294, 358-385): J d of every sample from the bender's divergence kernel in ray mode
                 // (value + tangent chain, fp32), then the network program on the per-sample directions (its training instantiation takes
@@ -2348,34 +2199,17 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
         hipError_t ge = hipSuccess;
         if (bend) ge = bender_pass(zc, S, bentA, a->coarse, 5);
         if (ge != hipSuccess) return NRNERF_ERR_HIP;
-        CompositeArgs gc{};
-        gc.rays = a->rays; gc.ray_stride = a->ray_stride;
-        gc.raw4 = raw_c; gc.z = zc; gc.n_rays = N; gc.S = S; gc.n_importance = I;
-        gc.lindisp = a->lindisp; gc.white_bkgd = a->white_bkgd; gc.noise = a->noise_coarse; gc.u = a->u_fine;
-        gc.vis = a->coarse.visibility_weights; gc.alpha = a->coarse.opacity_alpha;
-        if (I > 0) {
-            gc.rgb = a->rgb0 ? a->rgb0 : raw_f; gc.disp = a->disp0 ? a->disp0 : raw_f + (size_t)N * 3; gc.acc = a->acc0 ? a->acc0 : raw_f + (size_t)N * 4;
-            gc.z_std = a->z_std; gc.z_out = z_fine;
-        } else {
-            gc.rgb = a->rgb_map; gc.disp = a->disp_map; gc.acc = a->acc_map; gc.z_user = a->z_vals;
-            if (surface) { gc.bent4 = bent_final; gc.surf_pts = a->surface_pts; gc.surf_rig = a->surface_rigidity; gc.med_idx = a->median_index; }
-        }
+        const CompositeArgs gc = composite_args(/*final=*/I == 0, raw_c);
         bool fused_c = false, fused_f = false;
-        ge = network_pass(m->gen_coarse_prog, m->gen_coarse, zc, S, bend ? bentA : nullptr, raw_c, (I == 0) ? a->raw : nullptr,
+        ge = network_pass(m->gen_coarse.prog, m->gen_coarse, zc, S, bend ? bentA : nullptr, raw_c, (I == 0) ? a->raw : nullptr,
                           (I == 0 && surface) ? bent_final : nullptr, a->coarse, 0, (I == 0) ? &gc : nullptr, &fused_c);
         if (ge != hipSuccess) return NRNERF_ERR_HIP;
         if (!fused_c && timed(1, "composite_kernel", 0, 0, [&] { return launch_composite(gc, stream); }) != hipSuccess) return NRNERF_ERR_HIP;
         if (I == 0) return NRNERF_OK;
         if (bend) ge = bender_pass(z_fine, SF, bent_final, a->fine, 4);
         if (ge != hipSuccess) return NRNERF_ERR_HIP;
-        CompositeArgs gf{};
-        gf.rays = a->rays; gf.ray_stride = a->ray_stride;
-        gf.raw4 = raw_f; gf.z = z_fine; gf.n_rays = N; gf.S = SF; gf.n_importance = 0;
-        gf.white_bkgd = a->white_bkgd; gf.noise = a->noise_fine;
-        gf.rgb = a->rgb_map; gf.disp = a->disp_map; gf.acc = a->acc_map; gf.z_user = a->z_vals;
-        gf.vis = a->fine.visibility_weights; gf.alpha = a->fine.opacity_alpha;
-        if (surface) { gf.bent4 = bent_final; gf.surf_pts = a->surface_pts; gf.surf_rig = a->surface_rigidity; gf.med_idx = a->median_index; }
-        ge = network_pass(m->gen_fine_prog, m->gen_fine, z_fine, SF, bend ? bent_final : nullptr, raw_f, a->raw, surface ? bent_final : nullptr, a->fine, 2,
+        const CompositeArgs gf = composite_args(/*final=*/true, raw_f);
+        ge = network_pass(m->gen_fine.prog, m->gen_fine, z_fine, SF, bend ? bent_final : nullptr, raw_f, a->raw, surface ? bent_final : nullptr, a->fine, 2,
                           &gf, &fused_f);
         if (ge != hipSuccess) return NRNERF_ERR_HIP;
         if (!fused_f && timed(3, "composite_kernel", 0, 0, [&] { return launch_composite(gf, stream); }) != hipSuccess) return NRNERF_ERR_HIP;
@@ -2413,17 +2247,6 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
     // hierarchical render keeps its composite kernel: sample_pdf and the merge follow it there.
     // NRNERF_RENDER_UNFUSED_COMPOSITE keeps the separate launch (A/B and bit-identity tests).
     const bool unfused_composite = (a->flags & NRNERF_RENDER_UNFUSED_COMPOSITE) != 0;
-    auto final_composite = [&](int pass_S, const float* zv, const float* noise, const nrnerf_sample_outputs& so, const float* raw4) {
-        CompositeArgs c{};
-        c.rays = a->rays; c.ray_stride = a->ray_stride;
-        c.raw4 = raw4; c.z = zv; c.n_rays = N; c.S = pass_S; c.n_importance = 0;
-        c.lindisp = a->lindisp; c.white_bkgd = a->white_bkgd; c.noise = noise;
-        c.rgb = a->rgb_map; c.disp = a->disp_map; c.acc = a->acc_map;
-        c.z_std = nullptr; c.z_out = nullptr; c.z_user = a->z_vals;
-        c.vis = so.visibility_weights; c.alpha = so.opacity_alpha;
-        if (surface) { c.bent4 = bent4; c.surf_pts = a->surface_pts; c.surf_rig = a->surface_rigidity; c.med_idx = a->median_index; }
-        return c;
-    };
     // (small batches keep the separate launch: a fused pass hands out whole GROUPS of rays -- 4 rays = 24 blocks at 192 samples --
     //  where the plain mapping hands out 8-block tiles, so below one group per CU the plain mapping fills more of the chip)
     auto enough_rays_to_fuse = [&](int pass_S) {
@@ -2434,27 +2257,10 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
         return (long long)N >= rays_per_group * m->num_cus;
     };
     const bool fuse_coarse_only = I == 0 && !m->has_bend && !unfused_composite && S <= 256 && enough_rays_to_fuse(S);
-    if (fuse_coarse_only) { na.fuse_on = 1; na.fuse = final_composite(S, zc, a->noise_coarse, a->coarse, nullptr); na.raw4 = nullptr; }
+    if (fuse_coarse_only) { na.fuse_on = 1; na.fuse = composite_args(/*final=*/true, nullptr); na.raw4 = nullptr; }
     // ---- K1's arguments: coarse composite (+ sampling + merge when a fine pass follows)
-    CompositeArgs ca{};
-    ca.rays = a->rays; ca.ray_stride = a->ray_stride;
-    ca.raw4 = raw_c; ca.z = zc; ca.n_rays = N; ca.S = S; ca.n_importance = I;
-    ca.lindisp = a->lindisp; ca.white_bkgd = a->white_bkgd;
-    ca.noise = a->noise_coarse; ca.u = a->u_fine;
-    if (I > 0) {
-        // rgb0/disp0/acc0 are optional for the caller but the kernel always writes them: park them in raw_f
-        // (not yet written) when the caller passed NULL.
-        ca.rgb = a->rgb0 ? a->rgb0 : raw_f;
-        ca.disp = a->disp0 ? a->disp0 : raw_f + (size_t)N * 3;
-        ca.acc = a->acc0 ? a->acc0 : raw_f + (size_t)N * 4;
-        ca.z_std = a->z_std; ca.z_out = z_fine; ca.z_user = nullptr;
-        if (split) { ca.split_bent_in = bent_c; ca.split_bent_out = bent4; ca.z_new = z_new; ca.rank_new = rank_new; }
-    } else {
-        ca.rgb = a->rgb_map; ca.disp = a->disp_map; ca.acc = a->acc_map;
-        ca.z_std = nullptr; ca.z_out = nullptr; ca.z_user = a->z_vals;
-    }
-    ca.vis = a->coarse.visibility_weights; ca.alpha = a->coarse.opacity_alpha;
-    if (I == 0 && surface) { ca.bent4 = bent4; ca.surf_pts = a->surface_pts; ca.surf_rig = a->surface_rigidity; ca.med_idx = a->median_index; }
+    CompositeArgs ca = composite_args(/*final=*/I == 0, raw_c);
+    if (I > 0 && split) { ca.split_bent_in = bent_c; ca.split_bent_out = bent4; ca.z_new = z_new; ca.rank_new = rank_new; }
     // K1 inside K0 (north_star: "compositing fused into the ray loop"; train.py:889-920): on the split path's 16x16x32 coarse trunk a wave
     // owns whole rays, so compositing, sample_pdf and the merge run as its epilogue (net_kernel_x16<.., SAMPLE>: composite_kernel's own
     // code, same bits) and raw_c never reaches HBM.  NRNERF_RENDER_COARSE_EPILOGUE_ON / _OFF select per call; the default follows the
@@ -2470,12 +2276,7 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
     hipError_t e;
     if (split_coarse) {
         // KBc: stand-alone bender over the S coarse samples, then the coarse trunk on the bent points
-        BendArgs bc{};
-        bc.rays = a->rays; bc.ray_stride = a->ray_stride;
-        bc.latents = a->latents; bc.lat_stride = a->latent_stride;
-        bc.z = zc; bc.lindisp = a->lindisp; bc.rank = nullptr; bc.n_rays = N; bc.n_per_ray = S; bc.out_stride = S;
-        bc.bent4 = bent_c; bc.knobs = kn;
-        e = run_bender(bc, 5, S);
+        e = run_bender(5, zc, nullptr, S, S, bent_c, /*dynamic_shares=*/true);
         if (e != hipSuccess) return NRNERF_ERR_HIP;
         na.pts4 = bent_c; na.bent4 = nullptr;
         if (x16_coarse) {
@@ -2507,7 +2308,7 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
     nf.z = z_fine; nf.S = SF;
     nf.raw4 = raw_f; nf.raw_out = a->raw; nf.raw_ch = m->fine.output_ch;
     nf.ex = sample_out(a->fine);
-    // K3 inside K2 (see final_composite above) whenever K2 is a kernel without a fused bender
+    // K3 inside K2 (see the comment on compositing in the final pass above) whenever K2 is a kernel without a fused bender
     // the split path's trunk-only pass on the 16x16x32 kernel (nrnerf_net_x16.h) when the call wants no detail outputs
     // (NRNERF_RENDER_NO_X16: the 32x32x16 kernel of nrnerf_net_mb.h)
     // (read per call, like NRNERF_UNFUSED_COMPOSITE: the parity tests run both kernels in one process)
@@ -2515,15 +2316,10 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
     const long long x16_group = x16_rays_per_group(trunk_arch(m->arch_id), SF);          // (nrnerf_net_x16.hip: the kernel's own ray-group size)
     const bool fuse_fine = (split || !m->has_bend) && !unfused_composite && SF <= 256 &&
                            (x16 ? (long long)N >= x16_group * m->num_cus : enough_rays_to_fuse(SF));
-    if (fuse_fine) { nf.fuse_on = 1; nf.fuse = final_composite(SF, z_fine, a->noise_fine, a->fine, nullptr); nf.raw4 = nullptr; }
+    if (fuse_fine) { nf.fuse_on = 1; nf.fuse = composite_args(/*final=*/true, nullptr); nf.raw4 = nullptr; }
     if (split) {
         // KB: only the I importance samples go through the bender; the coarse samples' bent points are already in place
-        BendArgs ba{};
-        ba.rays = a->rays; ba.ray_stride = a->ray_stride;
-        ba.latents = a->latents; ba.lat_stride = a->latent_stride;
-        ba.z = z_new; ba.rank = rank_new; ba.n_rays = N; ba.n_per_ray = I; ba.out_stride = SF;
-        ba.bent4 = bent4; ba.knobs = kn;
-        e = run_bender(ba, 4, I);
+        e = run_bender(4, z_new, rank_new, I, SF, bent4, /*dynamic_shares=*/true);
         if (e != hipSuccess) return NRNERF_ERR_HIP;
         // K2: trunk + head on ready-made points (compiled architecture 0 without bender)
         nf.pts4 = bent4; nf.bent4 = nullptr;
@@ -2547,7 +2343,7 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
     if (fuse_fine) return NRNERF_OK;
 
     // ---- K3: fine composite
-    const CompositeArgs cf = final_composite(SF, z_fine, a->noise_fine, a->fine, raw_f);
+    const CompositeArgs cf = composite_args(/*final=*/true, raw_f);
     e = timed(3, "composite_kernel", 0, 0, [&] { return launch_composite(cf, stream); });
     if (e != hipSuccess) return NRNERF_ERR_HIP;
     return NRNERF_OK;
@@ -2612,8 +2408,8 @@ int generic_trunk_call(const nrnerf_model* m, const nrnerf_generic_trunk_args* a
     if (!m || !a || a->struct_size != sizeof(nrnerf_generic_trunk_args)) return NRNERF_ERR_INVALID;
     if (!m->generic || !m->gen_train_ok) return NRNERF_ERR_UNSUPPORTED;
     if (a->which < 0 || a->which > 1 || a->n_rays < 0 || a->n_samples < 1 || a->n_samples > NRNERF_MAX_SAMPLES || !a->acts) return NRNERF_ERR_INVALID;
-    const bool fine = a->which == 1 && !m->gen_fine_is_coarse;
-    const nrnerf_model::GenTrainNet& tn = m->gen_tn[fine ? 1 : 0];
+    const bool fine = a->which == 1 && !m->fine_is_coarse;
+    const GenTrainNet& tn = m->gen_tn[fine ? 1 : 0];
     if (!backward && (!a->pts4 || !a->raw4 || (tn.views && !a->dirs) || (tn.lat > 0 && !a->latents))) return NRNERF_ERR_INVALID;
     // the epilogue writes channels 0..3 of a row of `raw`, and channel 4 when raw_ch > 4: the row must hold them and the network must have them
     if (!backward && a->raw && (a->raw_ch < 4 || a->raw_ch > (fine ? m->gen_fine : m->gen_coarse).output_ch)) return NRNERF_ERR_INVALID;
@@ -2622,7 +2418,7 @@ int generic_trunk_call(const nrnerf_model* m, const nrnerf_generic_trunk_args* a
     DeviceGuard guard(m->device);
     if (!guard.ok) return NRNERF_ERR_HIP;
     const long long M = (long long)a->n_rays * a->n_samples;
-    GenArgs g = backward ? (fine ? m->gen_fine_bwd_prog : m->gen_coarse_bwd_prog) : (fine ? m->gen_fine_prog : m->gen_coarse_prog);
+    GenArgs g = backward ? (fine ? m->gen_fine_bwd.prog : m->gen_coarse_bwd.prog) : (fine ? m->gen_fine.prog : m->gen_coarse.prog);
     const PassDev& pd = backward ? (fine ? m->gen_fine_bwd : m->gen_coarse_bwd) : (fine ? m->gen_fine : m->gen_coarse);
     g.wstream = pd.stream; g.bias = pd.bias;
     g.n_rays = a->n_rays; g.S = a->n_samples;
@@ -2631,7 +2427,7 @@ int generic_trunk_call(const nrnerf_model* m, const nrnerf_generic_trunk_args* a
         // the forward pass on the width-class 16x16x32 kernel (nrnerf_gx16.h, SAVE: activations written from the registers) when it has this
         // trunk: bf16, plain head, no latent input columns; 0.55 of the matrix pipe's peak instead of the run-time-parameterised kernel's 0.07
         const PassDev& gx = (fine ? m->gx_fine : m->gx_coarse);
-        const GxMeta& gm = (fine ? m->gx_meta_fine : m->gx_meta_coarse);
+        const GxMeta& gm = (fine ? m->gx_fine.gx : m->gx_coarse.gx);
         if (gx.stream && m->precision == NRNERF_PREC_BF16 && !tn.views && tn.lat == 0 && tn.W % 4 == 0 && M < (1ll << 32) &&
             (long long)a->n_rays * ((a->n_samples + 15) / 16) < (1ll << 31)) {
             GxArgs x{};
@@ -2650,7 +2446,7 @@ int generic_trunk_call(const nrnerf_model* m, const nrnerf_generic_trunk_args* a
     } else {
         // backward-data on the width-class kernel's dataflow (nrnerf_gx16_bwd.h) when the forward call left its relu bits
         const PassDev& gxb = (fine ? m->gx_fine_bwd : m->gx_coarse_bwd);
-        const GxMeta& gmb = (fine ? m->gx_meta_fine_bwd : m->gx_meta_coarse_bwd);
+        const GxMeta& gmb = (fine ? m->gx_fine_bwd.gx : m->gx_coarse_bwd.gx);
         if (gxb.stream && a->relu_bits && !tn.views && tn.lat == 0 && M < (1ll << 32) && (long long)a->n_rays * ((a->n_samples + 15) / 16) < (1ll << 31)) {
             GxBwdArgs b{};
             b.d_raw4 = a->d_raw4; b.relu_bits = a->relu_bits; b.d_pre = a->d_pre; b.save_stride = M * tn.W; b.save_w = tn.W;
@@ -2693,9 +2489,9 @@ int nrnerf_generic_trunk_backward(const nrnerf_model* m, const nrnerf_generic_tr
 int nrnerf_model_trains_generic(const nrnerf_model* m) { return m ? ((m->generic && m->gen_train_ok) ? 1 : 0) : NRNERF_ERR_INVALID; }
 size_t nrnerf_generic_trunk_bits_bytes(const nrnerf_model* m, int32_t which, int32_t n_rays, int32_t n_samples) {
     if (!m || !m->generic || which < 0 || which > 1 || n_rays < 1 || n_samples < 1) return 0;
-    const bool fine = which == 1 && !m->gen_fine_is_coarse;
+    const bool fine = which == 1 && !m->fine_is_coarse;
     const PassDev& gxb = fine ? m->gx_fine_bwd : m->gx_coarse_bwd;
-    const GxMeta& gmb = fine ? m->gx_meta_fine_bwd : m->gx_meta_coarse_bwd;
+    const GxMeta& gmb = fine ? m->gx_fine_bwd.gx : m->gx_coarse_bwd.gx;
     if (!gxb.stream) return 0;
     return (size_t)gmb.depth * (size_t)n_rays * (size_t)((n_samples + 15) / 16) * 64 * (size_t)gx16_bits_bytes_per_lane(gmb.wc);
 }

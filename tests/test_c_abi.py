@@ -102,3 +102,24 @@ def test_render_from_plain_c_equals_the_python_boundary(tmp_path):
     assert np.array_equal(rgb_c, py["rgb_map"].cpu().numpy())
     assert np.array_equal(acc_c, py["acc_map"].cpu().numpy())
     assert np.array_equal(np.nan_to_num(disp_c), np.nan_to_num(py["disp_map"].cpu().numpy()))
+
+
+# nrnerf_workspace_bytes(NULL, N, S, I) as the library of commit 1c6e29a answers it: callers size and cache their workspaces by these figures
+_WORKSPACE_BYTES = {
+    1: {(64, 0): 68096, (64, 64): 73216, (64, 128): 75776, (600, 300): 122624},
+    700: {(64, 0): 1678592, (64, 64): 5128192, (64, 128): 6964992, (600, 300): 38916352},
+    65536: {(64, 0): 151060736, (64, 64): 474022144, (64, 128): 645988608, (600, 300): 3637313792},
+    196608: {(64, 0): 453050624, (64, 64): 1421934848, (64, 128): 1937834240, (600, 300): 10911809792},
+}
+
+
+def test_workspace_sizes_are_frozen():
+    """No GPU needed: the workspace of a render call is a pure function of (rays, samples, importance samples) -- ten 256-byte-aligned
+    slots and the work counters -- and must not move when the code that lays the slots out does; invalid shapes ask for 0 bytes."""
+    from nonrigid_nerf_amd import _lib
+    lib = _lib.load()
+    for n, row in _WORKSPACE_BYTES.items():
+        for (s, i), want in row.items():
+            assert lib.nrnerf_workspace_bytes(None, n, s, i) == want, (n, s, i)
+    for n, s, i in [(0, 64, 0), (-1, 64, 64), (5, 0, 0), (5, -3, 0), (5, 64, -1)]:
+        assert lib.nrnerf_workspace_bytes(None, n, s, i) == 0, (n, s, i)

@@ -1331,6 +1331,115 @@ def test_device_side_weight_refresh_equals_a_fresh_pack(cfg_kw, precision):
             assert torch.equal(a_, f_), k
 
 
+_GENERIC_REFRESH_SHAPES = [dict(N_importance=64, netwidth=192, netdepth=6),
+                           dict(N_importance=64, netdepth=7, netwidth=96, netwidth_fine=160, multires=6, multires_views=2, use_viewdirs=True),
+                           dict(N_importance=64, netdepth=6, netwidth=192, netwidth_fine=160, skips=(2,), use_viewdirs=True, approx_nonrigid_viewdirs=False)]
+
+
+@pytest.mark.parametrize("route", ["host", "device"])
+@pytest.mark.parametrize("cfg_kw", _GENERIC_REFRESH_SHAPES, ids=["plain_192", "viewdirs_96_160", "exact_viewdirs_192"])
+@pytest.mark.parametrize("precision", ["f32", "bf16"])
+def test_generic_handles_refresh_like_fresh_ones(cfg_kw, precision, route):
+    """The test above for architectures outside the compiled set, through both refresh routes (``nrnerf_model_update`` re-packing on
+    the host, ``nrnerf_model_update_device`` gathering on the device): a plain 192-wide trunk behind the default bender (layer programs,
+    width-class trunk images, the compiled stand-alone bender's 32x32 and 16x16x32 images), a view-dependent head on a non-compiled trunk
+    (layer programs; width-class images in bf16) and exact Jacobian directions (+ the bender's training images, which that render reads).
+    After in-place weight changes the refreshed handle must render what a freshly packed one renders -- bit for bit; with a view-dependent
+    head on the device route at the tolerances of the test above (the folded views layer: fp32 device GEMM vs fp64 host product)."""
+    cfg = SceneConfig(**cfg_kw)
+    scene = make_scene(cfg, 0)
+    rb, coarse, fine = build_modules(scene, device=DEV)
+    rays, latents = make_rays(700, 5, cfg)
+    rays, latents = rays.to(DEV), latents.to(DEV)
+    R.set_precision(precision)
+    I = cfg.N_importance
+    used = {"device": 0, "host": 0}
+    orig_dev, orig_host = R.Model.update_from_device, R.Model.update
+
+    def dev_route(self, *a, **k):
+        if route == "host":
+            return False
+        ok = orig_dev(self, *a, **k)
+        used["device"] += int(ok)
+        return ok
+
+    def host_route(self, *a, **k):
+        ok = orig_host(self, *a, **k)
+        used["host"] += int(ok)
+        return ok
+
+    with torch.no_grad():
+        m0 = R.get_model(coarse, fine, device=DEV)
+        assert m0.generic
+        before = m0.render(rays, latents, 64, I, retraw=True)["rgb_map"].clone()
+        for mod in (rb, coarse, fine):
+            for p_ in mod.parameters():
+                p_.mul_(1.03).add_(0.001)
+        R.Model.update_from_device, R.Model.update = dev_route, host_route
+        try:
+            m1 = R.get_model(coarse, fine, device=DEV)
+        finally:
+            R.Model.update_from_device, R.Model.update = orig_dev, orig_host
+        after = m1.render(rays, latents, 64, I, retraw=True)
+        fresh = R.Model(coarse, fine, precision, DEV).render(rays, latents, 64, I, retraw=True)
+    torch.cuda.synchronize()
+    assert m1 is m0 and used == {"device": int(route == "device"), "host": int(route == "host")}, "the handle must be refreshed in place, by this route"
+    assert (after["rgb_map"] - before).abs().max() > 1e-4
+    for k in fresh:
+        a_, f_ = torch.nan_to_num(after[k]).float(), torch.nan_to_num(fresh[k]).float()
+        if cfg.use_viewdirs and route == "device":
+            tol = 2e-5 if precision == "f32" else 2e-2
+            assert float((a_ - f_).abs().max()) <= tol * max(1.0, float(f_.abs().max())), (k, float((a_ - f_).abs().max()))
+        else:
+            assert torch.equal(a_, f_), k
+
+
+@pytest.mark.parametrize("family", ["compiled_split_and_training", "generic_width_class_and_backward"])
+def test_destroying_a_handle_frees_every_image(family):
+    """nrnerf_model_destroy returns all device memory of a handle: after one warm-up create / destroy, 20 more cycles leave the device's
+    free memory (``torch.cuda.mem_get_info``: the driver's figure, the library allocates with hipMalloc) exactly where it was.  bf16 handles,
+    which carry the most images: the compiled default shape (fused passes, split-bender trunks, 16x16x32 trunks and bender, training images)
+    and a non-compiled 192-wide trunk (layer programs and their backward programs, width-class trunks and theirs, the bender's images)."""
+    cfg = SceneConfig(N_importance=64) if family.startswith("compiled") else SceneConfig(N_importance=64, netwidth=192, netdepth=6)
+    rb, coarse, fine = build_modules(make_scene(cfg, 0), device=DEV)
+
+    def cycle():
+        m = R.Model(coarse, fine, "bf16", DEV)
+        assert m.generic == family.startswith("generic")
+        m.close()
+
+    cycle()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    free0 = torch.cuda.mem_get_info(torch.device(DEV))[0]
+    for _ in range(20):
+        cycle()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    free1 = torch.cuda.mem_get_info(torch.device(DEV))[0]
+    print(f"\n[create / destroy x 20, {family}] free bytes before {free0}, after {free1}, difference {free0 - free1}")
+    assert free1 == free0
+
+
+def test_workspace_of_a_generic_exact_handle_adds_the_jacobian_directions():
+    """nrnerf_workspace_bytes with a handle: only a generic handle with exact Jacobian view directions asks for more than the model-less
+    figure -- one [N, S + I, 3] fp32 array, 256-byte aligned."""
+    from nonrigid_nerf_amd import _lib
+    lib = _lib.load()
+    build = lambda **kw: build_modules(make_scene(SceneConfig(N_importance=64, **kw), 0), device=DEV)
+    _, coarse, fine = build(netdepth=6, netwidth=192, netwidth_fine=160, skips=(2,), use_viewdirs=True, approx_nonrigid_viewdirs=False)
+    exact = R.Model(coarse, fine, "f32", DEV)
+    _, coarse2, fine2 = build(netwidth=192, netdepth=6)
+    plain = R.Model(coarse2, fine2, "f32", DEV)
+    _, coarse3, fine3 = build(use_viewdirs=True, approx_nonrigid_viewdirs=False)
+    compiled = R.Model(coarse3, fine3, "f32", DEV)
+    assert exact.generic and plain.generic and not compiled.generic
+    for N, S, I in [(1, 64, 0), (700, 64, 64), (65536, 64, 128), (333, 600, 300)]:
+        base = lib.nrnerf_workspace_bytes(None, N, S, I)
+        assert lib.nrnerf_workspace_bytes(exact.handle, N, S, I) - base == (N * (S + I) * 12 + 255) // 256 * 256
+        assert lib.nrnerf_workspace_bytes(plain.handle, N, S, I) == base and lib.nrnerf_workspace_bytes(compiled.handle, N, S, I) == base
+
+
 @pytest.mark.parametrize("n_rays,cfg_kw,stochastic", [(1024, {}, False), (128, dict(use_viewdirs=True), False), (777, dict(ray_bending=False), False),
                                                       (1024, {}, True)],
                          ids=["1024_default", "128_viewdirs", "777_no_bender", "1024_stochastic"])

@@ -1702,3 +1702,90 @@ def test_encoding_rows_kernels_vs_torch_autograd(dtype, L, stride, n_lat):
         ref, = torch.autograd.grad(want, p, gsum[:, :n_enc], retain_graph=True)
         scale = float(ref.abs().max())
         assert (got[:, :3] - ref).abs().max().item() <= 1e-5 * scale and bool((got[:, 3] == 0).all())
+
+
+def _refresh_cases():
+    shapes = [("default", dict(N_importance=64)), ("narrow_128", dict(N_importance=64, netwidth=128)), ("viewdirs", dict(N_importance=64, use_viewdirs=True)),
+              ("generic_192", dict(N_importance=64, netwidth=192, netdepth=6))]
+    # (view-dependent head on the device route: the refreshed views layer -- feature_linear folded in by an fp32 device GEMM -- differs from
+    #  the host packer's by an ulp, test_device_side_weight_refresh_equals_a_fresh_pack; the host route covers that shape's images bit for bit)
+    return [pytest.param(kw, route, id=f"{name}-{route}") for name, kw in shapes for route in ("host", "device")
+            if not (kw.get("use_viewdirs") and route == "device")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cfg_kw,route", _refresh_cases())
+@pytest.mark.parametrize("precision", ["f32", "bf16"])
+def test_a_refreshed_handle_trains_like_a_fresh_one(precision, cfg_kw, route):
+    """The TRAINING images of a handle (transposed trunk weights, bender-less forward images of the view-dependent head, the bender's fp32
+    forward / backward images; off the compiled set the backward programs and the width-class trunks with theirs) follow a weight refresh
+    like the render images do: after an in-place change of every parameter, one training_loss(...).backward() on the cached handle --
+    refreshed by ``nrnerf_model_update`` (host) or ``nrnerf_model_update_device`` (device) -- gives the loss and every parameter / latent
+    gradient of the same iteration on copies of the modules, i.e. on a freshly created handle.  Bit for bit: the comparison two fresh handles
+    pass against each other (asserted here too, as the yardstick; run-to-run results are deterministic, profiles/r06_soak_determinism.txt)."""
+    import copy
+    from nonrigid_nerf_amd import training
+    cfg = SceneConfig(**cfg_kw)
+    scene = make_scene(cfg, 1)
+    rays, latents = make_rays(96, 3, cfg)
+    rays = rays.to(DEV)
+    target = torch.rand(96, 3, generator=torch.Generator().manual_seed(2)).to(DEV)
+    R.set_precision(precision)
+    w = dict(offsets_loss_weight=60.0, divergence_loss_weight=3.0, rigidity_loss_weight=5e-4, global_step=120000, N_iters=200000)
+
+    def iteration(mods):
+        rb, coarse, fine = mods
+        for p_ in _named(rb, coarse, fine).values():
+            p_.grad = None
+        lat = latents.to(DEV).requires_grad_(True)
+        kw = dict(network_fn=coarse, network_fine=fine, network_query_fn=None, N_samples=64, N_importance=64, perturb=1.0, raw_noise_std=1.0)
+        torch.manual_seed(11)
+        loss, _ = training.training_loss(rays, lat, target, kw, **w)
+        loss.mean().backward()
+        torch.cuda.synchronize()
+        grads = {k: p.grad.clone() for k, p in _named(rb, coarse, fine).items() if p.grad is not None}
+        grads[("latents", "")] = lat.grad.clone()
+        return loss.detach().clone(), grads
+
+    def clone(mods):
+        rb2, coarse2, fine2 = copy.deepcopy(mods[0]), copy.deepcopy(mods[1]), copy.deepcopy(mods[2])
+        coarse2.ray_bender, fine2.ray_bender = (rb2,), (rb2,)
+        return rb2, coarse2, fine2
+
+    mods = _modules(scene)
+    iteration(mods)                                   # creates and caches the handle, old weights
+    with torch.no_grad():
+        for p_ in _named(*mods).values():
+            p_.mul_(1.03).add_(0.001)
+    used = {"device": 0, "host": 0, "created": 0}
+    orig_dev, orig_host, orig_init = R.Model.update_from_device, R.Model.update, R.Model.__init__
+
+    def dev_route(self, *a, **k):
+        if route == "host":
+            return False
+        ok = orig_dev(self, *a, **k)
+        used["device"] += int(ok)
+        return ok
+
+    def host_route(self, *a, **k):
+        ok = orig_host(self, *a, **k)
+        used["host"] += int(ok)
+        return ok
+
+    def init(self, *a, **k):
+        used["created"] += 1
+        return orig_init(self, *a, **k)
+
+    R.Model.update_from_device, R.Model.update, R.Model.__init__ = dev_route, host_route, init
+    try:
+        loss_r, g_r = iteration(mods)
+    finally:
+        R.Model.update_from_device, R.Model.update, R.Model.__init__ = orig_dev, orig_host, orig_init
+    assert used["created"] == 0 and used[route] >= 1 and used["host" if route == "device" else "device"] == 0, used
+    loss_a, g_a = iteration(clone(mods))              # fresh handles (new modules: new cache entries), the changed weights
+    loss_b, g_b = iteration(clone(mods))
+    assert torch.equal(loss_a, loss_b) and set(g_a) == set(g_b) and all(torch.equal(g_a[k], g_b[k]) for k in g_a), "two fresh handles disagree"
+    assert torch.equal(loss_r, loss_a)
+    assert set(g_r) == set(g_a)
+    for k in g_a:
+        assert torch.equal(g_r[k], g_a[k]), (k, float((g_r[k] - g_a[k]).abs().max()))
