@@ -1974,6 +1974,345 @@ size_t nrnerf_workspace_bytes(const nrnerf_model* model, int32_t n_rays, int32_t
     return WorkspaceLayout(n_rays, n_samples, n_importance, model && model->generic && model->exact).total;
 }
 
+}  // extern "C"
+namespace {
+// ---- nrnerf_render decides, then launches: plan_render says which kernels a call takes (no HIP call, no side effect, no device pointer),
+// RenderCall launches them -- per pass a bender step, a network step, a compositing step.  A new kernel route touches: the family enum,
+// one rule in plan_render, one case in the executor.
+#ifndef NRN_COARSE_EPILOGUE_DEFAULT
+#define NRN_COARSE_EPILOGUE_DEFAULT 0
+#endif
+enum class BendStep { None, Fused, Compiled, Program };      // no bender / inside the network kernel / stand-alone compiled kernel / generic bender program
+// net_kernel with its fused bender / without one (a model without bender, the split path's trunk-only pass) / the 16x16x32 trunk (nrnerf_net_x16.h) /
+// the width-class 16x16x32 trunk (nrnerf_gx16.h) / the run-time-parameterised kernel (nrnerf_generic.h) / the same on exact Jacobian directions
+enum class NetFamily { NetBender, NetTrunk, NetX16, Gx16, Gen, GenExact };
+enum class CompStep { Launch, Epilogue, EpilogueSample };    // composite_kernel's own launch / the network kernel's epilogue / ... with sample_pdf and the merge
+struct PassPlan {
+    bool exists = false;
+    bool final = false;            // its maps are the call's outputs (the only pass, or the fine one); else rgb0 / disp0 / acc0, sample_pdf, merged depths
+    int which = 0, S = 0;          // 0: coarse, 1: fine; samples per ray
+    BendStep bend = BendStep::None;
+    int bend_n = 0, bend_stride = 0, bend_slot = 0;          // stand-alone bender: n_per_ray samples of every ray to rows of out_stride; profile slot 5 / 4
+    bool bend_rank = false, bend_dynamic = false;            // ... at row rank[.] of the ray (the importance samples); blocks handed out by a work counter
+    NetFamily net = NetFamily::NetTrunk;
+    ImageSlot image = IMG_COARSE;                            // the packed weights the network kernel reads (and the profile's flops per sample)
+    int dispatch = 0, net_slot = 0;                          // the launcher's architecture index / width class; profile slot 0 / 2 (composite: + 1)
+    const char* name = "";                                   // profile display name
+    bool trunk_counter = false;                              // net_kernel_x16: ray groups handed out by a work counter
+    CompStep comp = CompStep::Launch;
+};
+struct RenderPlan {
+    bool generic = false, split = false, surface = false;
+    bool bend_x16 = false;         // the stand-alone bender is the 16x16x32 kernel (else the 32x32x16 one)
+    bool counters_first = false;   // the work counters' memset node goes ahead of every launch of the call (else: with the first launch that takes one)
+    PassPlan coarse, fine;
+};
+
+bool no_detail_outputs(const nrnerf_sample_outputs& o) {
+    return !(o.visibility_weights || o.opacity_alpha || o.initial_input_pts || o.unmasked_offsets || o.masked_offsets || o.input_pts || o.rigidity_mask);
+}
+// the stand-alone bender kernels index their 32-sample blocks with 32 bits: beyond 2^31 blocks a pass stays on the other kernels
+bool block_index_fits(int N, int S) { return (long long)N * ((S + 31) / 32) < (1ll << 31); }
+// A pass' compositing as its network kernel's epilogue: at most 256 samples, and at least one GROUP of rays per CU -- a fused pass hands out whole
+// groups of rays (4 rays = 24 blocks at 192 samples) where the plain mapping hands out 8-block tiles, so below that the plain mapping fills more
+// of the chip.  The group is the kernel family's own.
+bool enough_rays_to_fuse(const nrnerf_model& m, const PassPlan& p, int N) {
+    long long group;
+    if (p.net == NetFamily::NetX16) group = x16_rays_per_group(p.dispatch, p.S);
+    else if (p.net == NetFamily::Gx16) group = gx16_rays_per_group(p.dispatch, p.S);
+    // waves per workgroup x rays per wave: fp32 kernels 4 x 1; 16-bit two-blocks-per-wave kernels 4 x (1 or 2); 16-bit one-block-per-wave
+    // kernels (architecture 5) 8 x 1
+    else group = (m.precision == NRNERF_PREC_F32) ? 4 : (m.arch_id == 5 ? 8 : ((((p.S + 31) / 32) & 1) ? 8 : 4));
+    return p.S <= 256 && (long long)N >= group * m.num_cus;
+}
+
+RenderPlan plan_render(const nrnerf_model& m, const nrnerf_render_args& a) {
+    const int N = a.n_rays, S = a.n_samples, I = a.n_importance;
+    auto flag = [&](unsigned f) { return (a.flags & f) != 0; };
+    const bool plain = !a.detailed_output, unfused = flag(NRNERF_RENDER_UNFUSED_COMPOSITE), dynamic = !flag(NRNERF_RENDER_FIXED_SHARES);
+    RenderPlan r;
+    r.generic = m.generic != 0;
+    r.surface = a.surface_pts || a.surface_rigidity || a.median_index;
+    // Split-bender path: bender, no view-dependent head, a fine pass, no per-sample detail outputs (those are written by the fused kernels), 8-bit
+    // ranks among the merged depths (<= 256 samples per ray).  NRNERF_RENDER_FUSED_FINE_BENDER keeps the fused fine pass (A/B and bit-identity tests).
+    r.split = m.split_ok && I > 0 && plain && no_detail_outputs(a.coarse) && no_detail_outputs(a.fine) && !flag(NRNERF_RENDER_FUSED_FINE_BENDER) &&
+              block_index_fits(N, imax(S, I)) && S + I <= 256;
+    // the stand-alone bender: the 16x16x32 kernel (nrnerf_bend_x16.h; "bf16" mode's single-product bender) unless the call asks for the 32x32x16
+    // one (NRNERF_RENDER_BENDER_32X32: the bit-identity tests against the fused-bender kernels)
+    r.bend_x16 = m.bend_x16.stream && !flag(NRNERF_RENDER_BENDER_32X32 | NRNERF_RENDER_NO_X16);
+    const bool bend_counters = r.bend_x16 && dynamic && m.num_cus <= BEND_COUNTERS_PER_LAUNCH;      // (one counter per pair of co-resident workgroups)
+    r.counters_first = bend_counters;
+    for (int which = 0; which < (I > 0 ? 2 : 1); ++which) {
+        PassPlan& p = which ? r.fine : r.coarse;
+        const nrnerf_sample_outputs& so = which ? a.fine : a.coarse;
+        p.exists = true; p.which = which; p.final = which == 1 || I == 0; p.S = which ? S + I : S;
+        p.net_slot = 2 * which; p.bend_slot = 5 - which;
+        bool trunk_only = false;
+        if (m.generic) {
+            // architecture outside the compiled set (nrnerf_generic.h): per pass the bender over ALL its samples (no split-bender trick: this route
+            // trades speed for generality), the canonical network on the bent points, compositing
+            if (m.has_bend) {
+                // the reference's own bender shape: the compiled stand-alone kernel (weights resident in LDS) when the pass wants no detail outputs.
+                // Fixed shares here: with all samples of a ray in one launch the counters measured SLOWER -- width 192: 1.72 -> 1.82 ms per fine
+                // pass, profiles/r06_dynamic_shares_ab.txt -- where the split path's launches gain 8 %
+                p.bend = (m.gen_compiled_bender >= 0 && no_detail_outputs(so) && block_index_fits(N, p.S)) ? BendStep::Compiled : BendStep::Program;
+                p.bend_n = p.bend_stride = p.S;
+            }
+            const bool own = which && !m.fine_is_coarse;        // (one network for both passes: the fine pass runs on the coarse images)
+            const ImageDev& gx = m.img[own ? IMG_GX_FINE : IMG_GX_COARSE];
+            p.net = NetFamily::Gen; p.image = own ? IMG_GEN_FINE : IMG_GEN_COARSE; p.name = "gen_kernel";
+            if (m.exact) {
+                p.net = NetFamily::GenExact; p.name = "gen_kernel (exact Jacobian directions)";
+            } else if (m.has_bend && gx.stream && !flag(NRNERF_RENDER_NO_X16) && no_detail_outputs(so) && plain && (long long)N * p.S < (1ll << 32)) {
+                // the width-class 16x16x32 trunk when the pass runs on ready-made points and wants no detail outputs (32-bit sample rows).  A FINAL
+                // pass takes its compositing as the epilogue; NRNERF_RENDER_UNFUSED_COMPOSITE keeps the launch (bit-identity tests)
+                p.net = NetFamily::Gx16; p.image = own ? IMG_GX_FINE : IMG_GX_COARSE; p.dispatch = gx.gx.wc;
+                if (p.final && !unfused && enough_rays_to_fuse(m, p, N)) p.comp = CompStep::Epilogue;
+                p.name = p.comp == CompStep::Epilogue ? "gx16_kernel + fused compositing" : "gx16_kernel";
+            }
+            continue;
+        }
+        // The 16x16x32 trunk-only kernel (nrnerf_net_x16.h) for the passes of the split path.  Per call (nrnerf_render_args::flags; the parity tests
+        // run the kernels side by side in one process): NRNERF_RENDER_NO_X16 = the 32x32x16 kernels of nrnerf_net_mb.h, NRNERF_RENDER_X16_FINE_ONLY =
+        // the fine pass only, default = the coarse pass too -- stand-alone bender over the S coarse samples + 16x16x32 trunk instead of the
+        // fused-bender 32x32x16 kernel.
+        const ImageSlot x16_image = which ? IMG_FINE_TRUNK_X16 : IMG_COARSE_TRUNK_X16;
+        const bool x16 = r.split && !flag(NRNERF_RENDER_NO_X16) && (which || !flag(NRNERF_RENDER_X16_FINE_ONLY)) && m.img[x16_image].stream && plain;
+        // The coarse pass stays fused by default: measured on MI355X (round 2), bender kernel 1.56 ms + trunk-only coarse kernel 8.72 ms = 10.28 ms
+        // against 10.22 ms fused -- nothing is saved there, unlike in the fine pass where a third of the samples skips the bender (only the I
+        // importance samples go through it; the coarse samples' bent points are already in place).  NRNERF_RENDER_SPLIT_COARSE splits it as well (A/B).
+        const bool split_pass = r.split && (which || flag(NRNERF_RENDER_SPLIT_COARSE) || x16);
+        p.image = (which && !m.fine_is_coarse) ? IMG_FINE : IMG_COARSE;
+        p.dispatch = m.exact ? 3 + m.arch_id : m.arch_id;
+        p.bend = m.has_bend ? BendStep::Fused : BendStep::None;
+        p.net = m.has_bend ? NetFamily::NetBender : NetFamily::NetTrunk;
+        if (split_pass) {
+            p.bend = BendStep::Compiled; p.bend_n = which ? I : S; p.bend_stride = p.S; p.bend_rank = which == 1; p.bend_dynamic = bend_counters;
+            p.net = x16 ? NetFamily::NetX16 : NetFamily::NetTrunk; p.dispatch = trunk_arch(m.arch_id); p.trunk_counter = x16 && dynamic;
+            p.image = x16 ? x16_image : (which ? IMG_FINE_TRUNK : IMG_COARSE_TRUNK);
+            trunk_only = !x16;
+        }
+        // Compositing fused into the FINAL pass' network kernel (north_star: "compositing fused into the ray loop"; the reference calls
+        // raw2outputs inline, train.py:943-950): the kernel variants without a fused bender let each wave own whole rays, keep their raw outputs
+        // in LDS and composite them itself (nrnerf_composite_ray.h: the composite kernel's own code, so the same bits).  The pass' raw array never
+        // exists and one launch goes.  NRNERF_RENDER_UNFUSED_COMPOSITE keeps the separate launch (A/B and bit-identity tests).
+        if (p.final && p.bend != BendStep::Fused && !unfused && enough_rays_to_fuse(m, p, N)) p.comp = CompStep::Epilogue;
+        // The coarse pass of a hierarchical render keeps its composite kernel (sample_pdf and the merge follow it there) -- unless it runs on the
+        // 16x16x32 trunk, where they can be its epilogue too (net_kernel_x16<.., SAMPLE>, train.py:889-920; raw_c never reaches HBM).
+        // NRNERF_RENDER_COARSE_EPILOGUE_ON / _OFF select per call; the default (off) follows the A/B on one box.
+        const bool epilogue_wanted = !flag(NRNERF_RENDER_COARSE_EPILOGUE_OFF) && (flag(NRNERF_RENDER_COARSE_EPILOGUE_ON) || NRN_COARSE_EPILOGUE_DEFAULT != 0);
+        if (!p.final && x16 && epilogue_wanted && !unfused && S <= x16_coarse_epilogue_max_samples() && enough_rays_to_fuse(m, p, N)) p.comp = CompStep::EpilogueSample;
+        const bool fused = p.comp != CompStep::Launch;
+        if (x16) p.name = p.comp == CompStep::EpilogueSample ? "net_kernel_x16 + fused compositing, sample_pdf, merge" : (fused ? "net_kernel_x16 + fused compositing" : "net_kernel_x16");
+        else if (trunk_only) p.name = fused ? "net_kernel (trunk only) + fused compositing" : "net_kernel (trunk only)";
+        else p.name = m.has_bend ? "net_kernel (fused bender)" : (fused ? "net_kernel + fused compositing" : "net_kernel");
+    }
+    return r;
+}
+
+// The launches of one call: the workspace carved once, then per pass (run_pass) a bender step, a network step and a compositing step.
+struct RenderCall {
+    const nrnerf_model* const m;
+    const nrnerf_render_args* const a;
+    const RenderPlan& plan;
+    const hipStream_t stream;
+    const int N = a->n_rays, I = a->n_importance;
+    Knobs kn{};
+    bool prof = false;
+    float *raw_c, *z_fine, *raw_f, *bent4_ws, *z_coarse, *bent_c, *z_new, *jdirs;
+    uint8_t* rank_new;
+    unsigned* counters;            // one counter per stand-alone bender launch of the call and per 16x16x32 trunk launch, 64 bytes apart
+    bool counters_zeroed = false;
+    const float* zc = nullptr;     // explicit coarse depths (stratified jitter), or null: the coarse spacing
+
+    RenderCall(const nrnerf_model* m_, const nrnerf_render_args* a_, const RenderPlan& plan_, const WorkspaceLayout& lay, hipStream_t stream_)
+        : m(m_), a(a_), plan(plan_), stream(stream_) {
+        void* const ws = a->workspace;
+        raw_c = lay.at<float>(ws, lay.raw_c);
+        z_fine = lay.at<float>(ws, lay.z_fine, I > 0);
+        raw_f = lay.at<float>(ws, lay.raw_f, I > 0);
+        bent4_ws = lay.at<float>(ws, lay.bent4);
+        z_coarse = lay.at<float>(ws, lay.z_coarse);
+        bent_c = lay.at<float>(ws, lay.bent_c, I > 0);
+        z_new = lay.at<float>(ws, lay.z_new, I > 0);
+        rank_new = lay.at<uint8_t>(ws, lay.rank_new, I > 0);
+        jdirs = lay.at<float>(ws, lay.jdirs, m->generic && m->exact);      // [N, S + I | S, 3]: exact Jacobian directions of the pass in flight
+        counters = lay.at<unsigned>(ws, lay.counters);
+        kn.has_cutoff = a->has_rigidity_cutoff; kn.cutoff = a->rigidity_cutoff;
+        kn.has_scaling = a->has_test_time_scaling; kn.scaling = a->test_time_scaling;
+        kn.has_removal = a->has_removal_threshold; kn.removal = a->removal_threshold;
+        kn.detailed = a->detailed_output;
+        std::lock_guard<std::mutex> g(m->prof_mu);
+        prof = m->prof_on;
+    }
+    // a launch's work counter(s), `at` words into the block -- zeroed by ONE memset node per call, ahead of its first use; nullptr: fixed shares
+    unsigned* counter(bool wanted, size_t at) {
+        if (!wanted || (!counters_zeroed && hipMemsetAsync(counters, 0, BEND_COUNTER_BYTES, stream) != hipSuccess)) return nullptr;
+        counters_zeroed = true;
+        return counters + at;
+    }
+    // the profile record of a launch over `samples` samples per ray on image `im`
+    nrnerf_model::Ev work(int slot, const char* name, const ImageDev& im, int samples) const {
+        const double n = (double)N * samples;
+        return {slot, nullptr, nullptr, n * im.algo_flops_per_sample, n * im.mfma_flops_per_sample, name};
+    }
+    template <class F> hipError_t timed(nrnerf_model::Ev ev, F&& launch) {
+        if (!prof) return launch();
+        // device-scope events (no system-scope cache write-back with every record).  Measured A/B against default events on
+        // one box: no difference (36.00 / 36.04 vs 36.14 / 35.99 ms per step) -- the kernels' event times add up to the step
+        // time within 0.05 ms either way, i.e. there are no launch gaps to recover between the five kernels of a render
+        if (hipEventCreateWithFlags(&ev.a, hipEventDisableSystemFence) != hipSuccess ||
+            hipEventCreateWithFlags(&ev.b, hipEventDisableSystemFence) != hipSuccess) return hipErrorUnknown;
+        (void)hipEventRecord(ev.a, stream);
+        const hipError_t e = launch();
+        (void)hipEventRecord(ev.b, stream);
+        std::lock_guard<std::mutex> g(m->prof_mu);
+        m->prof_events.push_back(ev);
+        return e;
+    }
+    // a layer program of a generic handle (the bender's, a network's) on the run-time-parameterised kernel
+    hipError_t run_program(const nrnerf_model::Ev& ev, const GenArgs& g) { return timed(ev, [&] { return launch_generic(m->precision, g, m->num_cus, stream); }); }
+    static SampleOut sample_out(const nrnerf_sample_outputs& o) {
+        return SampleOut{o.visibility_weights, o.opacity_alpha, o.initial_input_pts, o.unmasked_offsets, o.masked_offsets, o.input_pts, o.rigidity_mask};
+    }
+    const nrnerf_sample_outputs& outputs_of(const PassPlan& p) const { return p.which ? a->fine : a->coarse; }
+    const float* depths_of(const PassPlan& p) const { return p.which ? z_fine : zc; }
+    float* points_of(const PassPlan& p) const { return p.final ? bent4_ws : bent_c; }      // [N, S, 4]: a coarse pass has its own array when a fine pass follows
+    float* raw_of(const PassPlan& p) const { return p.which ? raw_f : raw_c; }              // [N, S, 4]: rgb + sigma, network kernel to composite kernel
+
+    // bend_n samples of every ray through the bender (the compiled stand-alone kernel or the generic bender program), bent points to points_of(p)
+    // -- at row rank_new[.] of the ray for the importance samples of the split path, else in order
+    hipError_t bender_step(const PassPlan& p) {
+        const float* const zv = p.bend_rank ? z_new : depths_of(p);
+        if (p.bend == BendStep::Program) {
+            const ImageDev& im = m->gen_bend;
+            GenArgs g = im.prog;
+            g.rays = a->rays; g.ray_stride = a->ray_stride; g.latents = a->latents; g.lat_stride = a->latent_stride;
+            g.z = zv; g.lindisp = a->lindisp; g.n_rays = N; g.S = p.bend_n;
+            g.wstream = im.stream; g.bias = im.bias;
+            g.bent4 = points_of(p); g.ex = sample_out(outputs_of(p)); g.knobs = kn;
+            return run_program(work(p.bend_slot, "gen_kernel (bender program)", im, p.bend_n), g);
+        }
+        const ImageDev& im = plan.bend_x16 ? m->bend_x16 : m->bend_only;
+        BendArgs b{};
+        b.rays = a->rays; b.ray_stride = a->ray_stride; b.latents = a->latents; b.lat_stride = a->latent_stride;
+        b.z = zv; b.lindisp = a->lindisp; b.rank = p.bend_rank ? rank_new : nullptr; b.n_rays = N; b.n_per_ray = p.bend_n; b.out_stride = p.bend_stride;
+        b.wstream = im.stream; b.bias = im.bias; b.bent4 = points_of(p); b.knobs = kn;
+        b.work_counter = counter(p.bend_dynamic, (size_t)16 * BEND_COUNTERS_PER_LAUNCH * p.which);
+        return timed(work(p.bend_slot, plan.bend_x16 ? "bend_kernel_x16" : "bend_kernel", im, p.bend_n), [&] {
+            return plan.bend_x16 ? launch_bend_x16(bender_arch_of(m), b, m->num_cus, stream) : launch_bend(m->precision, bender_arch_of(m), b, m->num_cus, stream);
+        });
+    }
+    // The compositing arguments of a pass: the call's maps for a final pass; else rgb0 / disp0 / acc0, sample_pdf and the merged depths of the fine pass
+    CompositeArgs composite_args(const PassPlan& p) const {
+        const bool fine = p.which == 1;
+        const nrnerf_sample_outputs& so = outputs_of(p);
+        CompositeArgs c{};
+        c.rays = a->rays; c.ray_stride = a->ray_stride;
+        c.raw4 = raw_of(p); c.z = depths_of(p); c.n_rays = N; c.S = p.S; c.n_importance = p.final ? 0 : I;
+        c.lindisp = a->lindisp; c.white_bkgd = a->white_bkgd; c.noise = fine ? a->noise_fine : a->noise_coarse;
+        c.vis = so.visibility_weights; c.alpha = so.opacity_alpha;
+        if (p.final) {
+            c.rgb = a->rgb_map; c.disp = a->disp_map; c.acc = a->acc_map; c.z_user = a->z_vals;
+            if (plan.surface) { c.bent4 = bent4_ws; c.surf_pts = a->surface_pts; c.surf_rig = a->surface_rigidity; c.med_idx = a->median_index; }
+        } else {
+            // rgb0/disp0/acc0 are optional for the caller but the kernel always writes them: park them in raw_f
+            // (not yet written) when the caller passed NULL.
+            c.u = a->u_fine;
+            c.rgb = a->rgb0 ? a->rgb0 : raw_f; c.disp = a->disp0 ? a->disp0 : raw_f + (size_t)N * 3; c.acc = a->acc0 ? a->acc0 : raw_f + (size_t)N * 4;
+            c.z_std = a->z_std; c.z_out = z_fine;
+            // split-bender path: the coarse samples' bent points move to their rows among the merged depths, the new samples are listed for the bender
+            if (plan.split) { c.split_bent_in = bent_c; c.split_bent_out = bent4_ws; c.z_new = z_new; c.rank_new = rank_new; }
+        }
+        return c;
+    }
+    // the network kernel of the pass; `c` (its compositing arguments) becomes the kernel's epilogue when the plan says so -- the pass' raw array
+    // (16 B per sample written and read back) then never exists
+    hipError_t network_step(const PassPlan& p, const CompositeArgs& c) {
+        const bool fused = p.comp != CompStep::Launch;
+        const ImageDev& im = m->img[p.image];
+        const nrnerf_sample_outputs& so = outputs_of(p);
+        const float* const pts = (p.bend == BendStep::Compiled || p.bend == BendStep::Program) ? points_of(p) : nullptr;      // ready-made points
+        // without them the kernel reports the points it evaluates where a later step reads them: the surface reduction, the split fine pass
+        float* const pts_out = (!pts && (p.final ? plan.surface : plan.split)) ? points_of(p) : nullptr;
+        float* const raw4 = fused ? nullptr : raw_of(p);
+        float* const raw_out = p.final ? a->raw : nullptr;
+        CompositeArgs fuse = fused ? c : CompositeArgs{};
+        fuse.raw4 = nullptr;
+        const nrnerf_model::Ev ev = work(p.net_slot, p.name, im, p.S);
+        switch (p.net) {
+        case NetFamily::NetBender: case NetFamily::NetTrunk: case NetFamily::NetX16: {
+            NetArgs n{};
+            n.rays = a->rays; n.ray_stride = a->ray_stride; n.latents = a->latents; n.lat_stride = a->latent_stride;
+            n.z = depths_of(p); n.lindisp = a->lindisp; n.pts4 = pts; n.n_rays = N; n.S = p.S;
+            n.wstream = im.stream; n.bias = im.bias;
+            n.raw4 = raw4; n.raw_out = raw_out; n.raw_ch = im.output_ch; n.bent4 = pts_out;
+            n.ex = sample_out(so); n.knobs = kn; n.fuse_on = fused; n.fuse = fuse;
+            return timed(ev, [&] {
+                if (p.net != NetFamily::NetX16) return launch_net(m->precision, p.net == NetFamily::NetBender, m->views, p.dispatch, n, m->num_cus, stream);
+                n.work_counter = counter(p.trunk_counter, (size_t)16 * BEND_COUNTERS_PER_LAUNCH * 2 + 16 * p.which);
+                return launch_net_x16(m->precision, p.dispatch, m->views, n, m->num_cus, stream);
+            });
+        }
+        case NetFamily::Gx16: {
+            const GxMeta& gm = im.gx;
+            GxArgs x{};
+            x.pts4 = pts; x.raw4 = raw4; x.raw_out = raw_out; x.raw_ch = im.output_ch;
+            x.n_rays = N; x.S = p.S; x.wstream = im.stream; x.bias = im.bias;
+            x.depth = gm.depth; x.skip = gm.skip; x.L = gm.L; x.n_bias_tiles = gm.n_bias_tiles; x.LV = gm.LV;
+            x.fuse_on = fused; x.fuse = fuse;
+            return timed(ev, [&] { return launch_gx16(m->precision, p.dispatch, gm.views != 0, x, m->num_cus, stream); });
+        }
+        case NetFamily::Gen: {
+            GenArgs g = im.prog;
+            g.rays = a->rays; g.ray_stride = a->ray_stride; g.latents = a->latents; g.lat_stride = a->latent_stride;
+            g.z = depths_of(p); g.lindisp = a->lindisp; g.n_rays = N; g.S = p.S;
+            g.pts4 = pts; g.dirs_from_pts = (pts && m->views) ? 1 : 0;
+            g.wstream = im.stream; g.bias = im.bias;
+            g.raw4 = raw4; g.raw_out = raw_out; g.raw_ch = im.output_ch;
+            g.bent4 = pts ? const_cast<float*>(pts) : pts_out;          // with a bender: read (removal knob); without: written (points of the pass)
+            g.knobs = kn;
+            if (!pts) g.ex = sample_out(so);                             // without a bender the network kernel reports the points
+            return run_program(ev, g);
+        }
+        case NetFamily::GenExact: {
+            // exact Jacobian view directions (rnh:291-294, 358-385): J d of every sample from the bender's divergence kernel in ray mode
+            // (value + tangent chain, fp32), then the network program on the per-sample directions (its training instantiation takes
+            // them; nothing is saved)
+            BendDivArgs t{};
+            t.latents = a->latents; t.lat_stride = a->latent_stride; t.m = (long long)N * p.S;
+            t.wstream = m->bend_train_fwd.stream; t.bias = m->bend_train_fwd.bias;
+            t.knobs.has_cutoff = kn.has_cutoff; t.knobs.cutoff = kn.cutoff; t.knobs.has_scaling = kn.has_scaling; t.knobs.scaling = kn.scaling;
+            t.rays = a->rays; t.ray_stride = a->ray_stride; t.zr = depths_of(p); t.S = p.S; t.lindisp = a->lindisp; t.dirs_out = jdirs;
+            const bool b16 = m->precision != NRNERF_PREC_F32;
+            const hipError_t je = (m->gen_compiled_bender == 0) ? launch_bend_div_fwd_a0(t, m->num_cus, stream, b16) : launch_bend_div_fwd_a1(t, m->num_cus, stream, b16);
+            if (je != hipSuccess) return je;
+            GenArgs g = im.prog;
+            g.mode = 1;
+            g.rays = pts; g.ray_stride = 0; g.latents = nullptr; g.lat_stride = 0;
+            g.z = nullptr; g.lindisp = 0; g.n_rays = N; g.S = p.S;
+            g.pts4 = pts; g.dirs_from_pts = 0; g.dirs = jdirs;
+            g.wstream = im.stream; g.bias = im.bias;
+            g.raw4 = raw4; g.raw_out = raw_out; g.raw_ch = im.output_ch; g.bent4 = const_cast<float*>(pts);        // (read: the removal knob, rnh:308-311)
+            g.save = nullptr; g.mask = nullptr; g.save_stride = 0; g.save_w = 0;
+            g.knobs = kn;
+            return timed(ev, [&] { return launch_generic_train(m->precision, g, m->num_cus, stream); });
+        }
+        }
+        return hipErrorUnknown;
+    }
+    int run_pass(const PassPlan& p) {
+        if ((p.bend == BendStep::Compiled || p.bend == BendStep::Program) && bender_step(p) != hipSuccess) return NRNERF_ERR_HIP;
+        const CompositeArgs c = composite_args(p);
+        if (network_step(p, c) != hipSuccess) return NRNERF_ERR_HIP;
+        if (p.comp != CompStep::Launch) return NRNERF_OK;      // (the network kernel took it as its epilogue)
+        const nrnerf_model::Ev ev{p.net_slot + 1, nullptr, nullptr, 0, 0, "composite_kernel"};
+        return timed(ev, [&] { return launch_composite(c, stream); }) == hipSuccess ? NRNERF_OK : NRNERF_ERR_HIP;
+    }
+};
+}  // namespace
+extern "C" {
+
 int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_stream) try {
     if (!m || !a || a->struct_size != sizeof(nrnerf_render_args)) return NRNERF_ERR_INVALID;
     if (a->n_rays < 0 || a->n_samples < 2 || a->n_importance < 0) return NRNERF_ERR_INVALID;
@@ -1985,368 +2324,22 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
     const size_t need = nrnerf_workspace_bytes(m, a->n_rays, a->n_samples, a->n_importance);      // (= WorkspaceLayout::total below)
     if (!a->workspace || a->workspace_bytes < need || ((uintptr_t)a->workspace & 255)) return NRNERF_ERR_WORKSPACE;
     hipStream_t stream = (hipStream_t)hip_stream;
-    const int N = a->n_rays, S = a->n_samples, I = a->n_importance, SF = S + I;
     // launches go to the model's device whatever the calling thread's current device is (restored on every exit path)
     DeviceGuard guard(m->device);
     if (!guard.ok) return NRNERF_ERR_HIP;
-
-    const WorkspaceLayout lay(N, S, I, m->generic && m->exact);
-    void* const ws = a->workspace;
-    float* const raw_c = lay.at<float>(ws, lay.raw_c);
-    float* const z_fine = lay.at<float>(ws, lay.z_fine, I > 0);
-    float* const raw_f = lay.at<float>(ws, lay.raw_f, I > 0);
-    const bool surface = a->surface_pts || a->surface_rigidity || a->median_index;
-    float* const bent4_ws = lay.at<float>(ws, lay.bent4);       // (the slot itself: `bent4` is null when the compiled path does not need it)
-    float* const z_coarse = lay.at<float>(ws, lay.z_coarse);
-    // Split-bender path: bender, no view-dependent head, a fine pass, no per-sample detail outputs (those are written by
-    // the fused kernels).  NRNERF_RENDER_FUSED_FINE_BENDER keeps the fused fine pass (A/B and bit-identity tests).
-    auto any_detail = [](const nrnerf_sample_outputs& o) {
-        return o.visibility_weights || o.opacity_alpha || o.initial_input_pts || o.unmasked_offsets || o.masked_offsets ||
-               o.input_pts || o.rigidity_mask;
-    };
-    const bool force_fused = (a->flags & NRNERF_RENDER_FUSED_FINE_BENDER) != 0;
-    // (the stand-alone bender kernel indexes its 32-sample blocks with 32 bits: beyond 2^31 blocks stay on the fused kernels)
-    // (8-bit ranks among the merged depths: beyond 256 samples per ray the fused-bender fine pass renders)
-    const bool split = m->split_ok && I > 0 && !a->detailed_output && !any_detail(a->coarse) && !any_detail(a->fine) && !force_fused &&
-                       (long long)N * ((imax(S, I) + 31) / 32) < (1ll << 31) && SF <= 256;
-    float* const bent4 = (surface || split) ? bent4_ws : nullptr;
-    float* const bent_c = lay.at<float>(ws, lay.bent_c, I > 0);
-    float* const z_new = lay.at<float>(ws, lay.z_new, I > 0);
-    uint8_t* const rank_new = lay.at<uint8_t>(ws, lay.rank_new, I > 0);
-    float* const jdirs = lay.at<float>(ws, lay.jdirs, m->generic && m->exact);      // [N, S + I | S, 3]: exact Jacobian directions of the pass in flight
-    // one counter per stand-alone bender launch of the call (64 bytes apart), zeroed by ONE memset node ahead of the first launch
-    unsigned* const bend_counters = lay.at<unsigned>(ws, lay.counters);
-    bool counters_zeroed = false;
-    auto zeroed_counters = [&]() -> unsigned* {              // (the block, zeroed once per call; nullptr: the kernels' fixed shares)
-        if (!counters_zeroed && hipMemsetAsync(bend_counters, 0, BEND_COUNTER_BYTES, stream) != hipSuccess) return nullptr;
-        counters_zeroed = true;
-        return bend_counters;
-    };
-    auto bend_counter = [&](int which) -> unsigned* {      // (per launch: one counter per pair of co-resident workgroups, 64 bytes apart)
-        unsigned* const c = m->num_cus > BEND_COUNTERS_PER_LAUNCH ? nullptr : zeroed_counters();
-        return c ? c + (size_t)16 * BEND_COUNTERS_PER_LAUNCH * which : nullptr;
-    };
-    auto trunk_counter = [&](int which) -> unsigned* {     // (0: coarse pass, 1: fine pass)
-        unsigned* const c = (a->flags & NRNERF_RENDER_FIXED_SHARES) ? nullptr : zeroed_counters();
-        return c ? c + (size_t)16 * BEND_COUNTERS_PER_LAUNCH * 2 + 16 * which : nullptr;
-    };
-    if ((a->u_fine || a->noise_fine) && I == 0) return NRNERF_ERR_INVALID;
-
-    Knobs kn{};
-    kn.has_cutoff = a->has_rigidity_cutoff; kn.cutoff = a->rigidity_cutoff;
-    kn.has_scaling = a->has_test_time_scaling; kn.scaling = a->test_time_scaling;
-    kn.has_removal = a->has_removal_threshold; kn.removal = a->removal_threshold;
-    kn.detailed = a->detailed_output;
-
-    bool prof;
-    { std::lock_guard<std::mutex> g(m->prof_mu); prof = m->prof_on; }
-    auto timed = [&](int kernel, const char* name, double flops, double mfma, auto&& launch) -> hipError_t {
-        if (!prof) return launch();
-        nrnerf_model::Ev ev{kernel, nullptr, nullptr, flops, mfma, name};
-        // device-scope events (no system-scope cache write-back with every record).  Measured A/B against default events on
-        // one box: no difference (36.00 / 36.04 vs 36.14 / 35.99 ms per step) -- the kernels' event times add up to the step
-        // time within 0.05 ms either way, i.e. there are no launch gaps to recover between the five kernels of a render
-        if (hipEventCreateWithFlags(&ev.a, hipEventDisableSystemFence) != hipSuccess ||
-            hipEventCreateWithFlags(&ev.b, hipEventDisableSystemFence) != hipSuccess) return hipErrorUnknown;
-        (void)hipEventRecord(ev.a, stream);
-        hipError_t e = launch();
-        (void)hipEventRecord(ev.b, stream);
-        std::lock_guard<std::mutex> g(m->prof_mu);
-        m->prof_events.push_back(ev);
-        return e;
-    };
-
-    auto sample_out = [](const nrnerf_sample_outputs& o) {
-        return SampleOut{o.visibility_weights, o.opacity_alpha, o.initial_input_pts, o.unmasked_offsets,
-                         o.masked_offsets, o.input_pts, o.rigidity_mask};
-    };
-
-    // the stand-alone bender of the split path: the 16x16x32 kernel (nrnerf_bend_x16.h; "bf16" mode's single-product bender) unless the call
-    // asks for the 32x32x16 one (NRNERF_RENDER_BENDER_32X32: the bit-identity tests against the fused-bender kernels)
-    const bool bend_x16 = m->bend_x16.stream && !(a->flags & (NRNERF_RENDER_BENDER_32X32 | NRNERF_RENDER_NO_X16));
-    if (bend_x16 && !(a->flags & NRNERF_RENDER_FIXED_SHARES)) (void)bend_counter(0);       // (the memset node ahead of every timed launch)
+    const WorkspaceLayout lay(a->n_rays, a->n_samples, a->n_importance, m->generic && m->exact);
+    if ((a->u_fine || a->noise_fine) && a->n_importance == 0) return NRNERF_ERR_INVALID;
+    const RenderPlan plan = plan_render(*m, *a);
+    RenderCall call(m, a, plan, lay, stream);
+    if (plan.counters_first) (void)call.counter(true, 0);      // (the memset node ahead of every timed launch)
     // ---- stratified jitter of the coarse depths (perturb > 0): both coarse kernels then read explicit depths
-    const float* zc = nullptr;
     if (a->u_coarse) {
-        JitterArgs ja{a->rays, a->ray_stride, a->u_coarse, N, S, a->lindisp, z_coarse};
+        JitterArgs ja{a->rays, a->ray_stride, a->u_coarse, a->n_rays, a->n_samples, a->lindisp, call.z_coarse};
         if (launch_zjitter(ja, stream) != hipSuccess) return NRNERF_ERR_HIP;
-        zc = z_coarse;
+        call.zc = call.z_coarse;
     }
-
-    // `n_per_ray` samples of every ray at depths zv (null: the coarse spacing) through the bender, bent points to out4 [N, out_stride, 4] -- at
-    // row rank[.] of the ray when `rank` is given, else in order.  Profile slot 5 / 4: the coarse / fine pass.  `dynamic_shares`: the 16x16x32
-    // kernel hands its blocks out through a work counter (unless NRNERF_RENDER_FIXED_SHARES)
-    auto run_bender = [&](int slot, const float* zv, const uint8_t* rank, int n_per_ray, int out_stride, float* out4, bool dynamic_shares) -> hipError_t {
-        BendArgs b{};
-        b.rays = a->rays; b.ray_stride = a->ray_stride; b.latents = a->latents; b.lat_stride = a->latent_stride;
-        b.z = zv; b.lindisp = a->lindisp; b.rank = rank; b.n_rays = N; b.n_per_ray = n_per_ray; b.out_stride = out_stride;
-        b.bent4 = out4; b.knobs = kn;
-        const int arch = bender_arch_of(m);
-        const ImageDev& im = bend_x16 ? m->bend_x16 : m->bend_only;
-        b.wstream = im.stream; b.bias = im.bias;
-        const double samples = (double)N * n_per_ray;
-        if (bend_x16) {
-            b.work_counter = (dynamic_shares && !(a->flags & NRNERF_RENDER_FIXED_SHARES)) ? bend_counter(slot == 5 ? 0 : 1) : nullptr;
-            return timed(slot, "bend_kernel_x16", samples * im.algo_flops_per_sample, samples * im.mfma_flops_per_sample,
-                         [&] { return launch_bend_x16(arch, b, m->num_cus, stream); });
-        }
-        return timed(slot, "bend_kernel", samples * im.algo_flops_per_sample, samples * im.mfma_flops_per_sample,
-                     [&] { return launch_bend(m->precision, arch, b, m->num_cus, stream); });
-    };
-    // The compositing arguments of a pass.  `final`: the pass whose maps are the call's outputs (the only pass, or the fine one) -- raw4 null
-    // when they are the epilogue of the pass' network kernel; else the coarse pass of a hierarchical render: rgb0 / disp0 / acc0, sample_pdf and
-    // the merged depths of the fine pass
-    auto composite_args = [&](bool final, const float* raw4) {
-        const bool fine = final && I > 0;
-        const nrnerf_sample_outputs& so = fine ? a->fine : a->coarse;
-        CompositeArgs c{};
-        c.rays = a->rays; c.ray_stride = a->ray_stride;
-        c.raw4 = raw4; c.z = fine ? z_fine : zc; c.n_rays = N; c.S = fine ? SF : S; c.n_importance = final ? 0 : I;
-        c.lindisp = a->lindisp; c.white_bkgd = a->white_bkgd; c.noise = fine ? a->noise_fine : a->noise_coarse;
-        c.vis = so.visibility_weights; c.alpha = so.opacity_alpha;
-        if (final) {
-            c.rgb = a->rgb_map; c.disp = a->disp_map; c.acc = a->acc_map; c.z_user = a->z_vals;
-            if (surface) { c.bent4 = bent4_ws; c.surf_pts = a->surface_pts; c.surf_rig = a->surface_rigidity; c.med_idx = a->median_index; }
-        } else {
-            // rgb0/disp0/acc0 are optional for the caller but the kernel always writes them: park them in raw_f
-            // (not yet written) when the caller passed NULL.
-            c.u = a->u_fine;
-            c.rgb = a->rgb0 ? a->rgb0 : raw_f; c.disp = a->disp0 ? a->disp0 : raw_f + (size_t)N * 3; c.acc = a->acc0 ? a->acc0 : raw_f + (size_t)N * 4;
-            c.z_std = a->z_std; c.z_out = z_fine;
-        }
-        return c;
-    };
-
-    if (m->generic) {
-        // ---- architecture outside the compiled set (nrnerf_generic.h): per pass the bender over all samples of the pass (no
-        //      split-bender trick: the generic path trades speed for generality), the canonical network on the bent points,
-        //      the composite kernel.  Kernel slots of the profile: 5 / 4 = bender of the coarse / fine pass.
-        const bool bend = m->has_bend != 0, views = m->views != 0;
-        auto bender_pass = [&](const float* zv, int nS, float* out4, const nrnerf_sample_outputs& so, int slot) -> hipError_t {
-            if (m->gen_compiled_bender >= 0 && !any_detail(so) && (long long)N * ((nS + 31) / 32) < (1ll << 31)) {
-                // the reference's own bender shape: the compiled stand-alone kernel (weights resident in LDS), all nS samples of a ray
-                // (fixed shares here: with all nS samples of a ray in one launch the counters measured SLOWER -- width 192: 1.72 -> 1.82 ms
-                //  per fine pass, profiles/r06_dynamic_shares_ab.txt -- where the split path's launches gain 8 %)
-                return run_bender(slot, zv, nullptr, nS, nS, out4, /*dynamic_shares=*/false);
-            }
-            GenArgs g = m->gen_bend.prog;
-            g.rays = a->rays; g.ray_stride = a->ray_stride; g.latents = a->latents; g.lat_stride = a->latent_stride;
-            g.z = zv; g.lindisp = a->lindisp; g.n_rays = N; g.S = nS;
-            g.wstream = m->gen_bend.stream; g.bias = m->gen_bend.bias;
-            g.bent4 = out4; g.ex = sample_out(so); g.knobs = kn;
-            return timed(slot, "gen_kernel (bender program)", (double)N * nS * m->gen_bend.algo_flops_per_sample, 0, [&] { return launch_generic(m->precision, g, m->num_cus, stream); });
-        };
-        // `fuse` (a FINAL pass): its compositing arguments -- taken as the kernel's epilogue when the pass runs on the width-class kernel
-        // (then *fused = true and the caller skips the composite launch); NRNERF_RENDER_UNFUSED_COMPOSITE keeps the launch (bit-identity tests)
-        auto network_pass = [&](const GenArgs& prog, const PassDev& pd, const float* zv, int nS, const float* pts, float* raw4, float* raw_user,
-                                float* bent_out, const nrnerf_sample_outputs& so, int slot, const CompositeArgs* fuse = nullptr,
-                                bool* fused = nullptr) -> hipError_t {
-            // the trunk on the width-class 16x16x32 kernel (nrnerf_gx16.h) when the pass runs on ready-made points and wants no detail outputs
-            const ImageDev& gxu = (&pd == &m->gen_coarse) ? m->gx_coarse : m->gx_fine;      // (one network for both passes: gen_fine IS gen_coarse)
-            const GxMeta& gmu = gxu.gx;
-            if (m->exact) {
-                // exact Jacobian view directions (rnh:291-294, 358-385): J d of every sample from the bender's divergence kernel in ray mode
-                // (value + tangent chain, fp32), then the network program on the per-sample directions (its training instantiation takes
-                // them; nothing is saved)
-                BendDivArgs t{};
-                t.latents = a->latents; t.lat_stride = a->latent_stride; t.m = (long long)N * nS;
-                t.wstream = m->bend_train_fwd.stream; t.bias = m->bend_train_fwd.bias;
-                t.knobs.has_cutoff = kn.has_cutoff; t.knobs.cutoff = kn.cutoff; t.knobs.has_scaling = kn.has_scaling; t.knobs.scaling = kn.scaling;
-                t.rays = a->rays; t.ray_stride = a->ray_stride; t.zr = zv; t.S = nS; t.lindisp = a->lindisp; t.dirs_out = jdirs;
-                const bool b16 = m->precision != NRNERF_PREC_F32;
-                hipError_t je = (m->gen_compiled_bender == 0) ? launch_bend_div_fwd_a0(t, m->num_cus, stream, b16) : launch_bend_div_fwd_a1(t, m->num_cus, stream, b16);
-                if (je != hipSuccess) return je;
-                GenArgs g = prog;
-                g.mode = 1;
-                g.rays = pts; g.ray_stride = 0; g.latents = nullptr; g.lat_stride = 0;
-                g.z = nullptr; g.lindisp = 0; g.n_rays = N; g.S = nS;
-                g.pts4 = pts; g.dirs_from_pts = 0; g.dirs = jdirs;
-                g.wstream = pd.stream; g.bias = pd.bias;
-                g.raw4 = raw4; g.raw_out = raw_user; g.raw_ch = pd.output_ch; g.bent4 = const_cast<float*>(pts);        // (read: the removal knob, rnh:308-311)
-                g.save = nullptr; g.mask = nullptr; g.save_stride = 0; g.save_w = 0;
-                g.knobs = kn;
-                return timed(slot, "gen_kernel (exact Jacobian directions)", (double)N * nS * pd.algo_flops_per_sample, (double)N * nS * pd.mfma_flops_per_sample,
-                             [&] { return launch_generic_train(m->precision, g, m->num_cus, stream); });
-            }
-            if (pts && gxu.stream && !(a->flags & NRNERF_RENDER_NO_X16) && !any_detail(so) && !kn.detailed &&
-                (long long)N * nS < (1ll << 32)) {      // (the kernel's 32-bit sample rows; beyond: the run-time-parameterised kernel below)
-                GxArgs x{};
-                x.pts4 = pts; x.raw4 = raw4; x.raw_out = raw_user; x.raw_ch = pd.output_ch;
-                x.n_rays = N; x.S = nS; x.wstream = gxu.stream; x.bias = gxu.bias;
-                x.depth = gmu.depth; x.skip = gmu.skip; x.L = gmu.L; x.n_bias_tiles = gmu.n_bias_tiles; x.LV = gmu.LV;
-                if (fuse && !(a->flags & NRNERF_RENDER_UNFUSED_COMPOSITE) && nS <= 256 &&
-                    (long long)N >= gx16_rays_per_group(gmu.wc, nS) * m->num_cus) {
-                    x.fuse_on = 1; x.fuse = *fuse; x.fuse.raw4 = nullptr; x.raw4 = nullptr;
-                    *fused = true;
-                }
-                return timed(slot, (x.fuse_on ? "gx16_kernel + fused compositing" : "gx16_kernel"), (double)N * nS * gxu.algo_flops_per_sample, (double)N * nS * gxu.mfma_flops_per_sample,
-                             [&] { return launch_gx16(m->precision, gmu.wc, gmu.views != 0, x, m->num_cus, stream); });
-            }
-            GenArgs g = prog;
-            g.rays = a->rays; g.ray_stride = a->ray_stride; g.latents = a->latents; g.lat_stride = a->latent_stride;
-            g.z = zv; g.lindisp = a->lindisp; g.n_rays = N; g.S = nS;
-            g.pts4 = pts; g.dirs_from_pts = (pts && views) ? 1 : 0;
-            g.wstream = pd.stream; g.bias = pd.bias;
-            g.raw4 = raw4; g.raw_out = raw_user; g.raw_ch = pd.output_ch;
-            g.bent4 = pts ? const_cast<float*>(pts) : bent_out;          // with a bender: read (removal knob); without: written (points of the pass)
-            g.knobs = kn;
-            if (!pts) g.ex = sample_out(so);                             // without a bender the network kernel reports the points
-            return timed(slot, "gen_kernel", (double)N * nS * pd.algo_flops_per_sample, (double)N * nS * pd.mfma_flops_per_sample,
-                         [&] { return launch_generic(m->precision, g, m->num_cus, stream); });
-        };
-        float* const bent_final = bent4_ws;                         // points of the final pass [N, S + I | S, 4]
-        float* const bentA = (I > 0) ? bent_c : bent4_ws;           // points of the coarse pass: its own array when a fine pass follows
-        hipError_t ge = hipSuccess;
-        if (bend) ge = bender_pass(zc, S, bentA, a->coarse, 5);
-        if (ge != hipSuccess) return NRNERF_ERR_HIP;
-        const CompositeArgs gc = composite_args(/*final=*/I == 0, raw_c);
-        bool fused_c = false, fused_f = false;
-        ge = network_pass(m->gen_coarse.prog, m->gen_coarse, zc, S, bend ? bentA : nullptr, raw_c, (I == 0) ? a->raw : nullptr,
-                          (I == 0 && surface) ? bent_final : nullptr, a->coarse, 0, (I == 0) ? &gc : nullptr, &fused_c);
-        if (ge != hipSuccess) return NRNERF_ERR_HIP;
-        if (!fused_c && timed(1, "composite_kernel", 0, 0, [&] { return launch_composite(gc, stream); }) != hipSuccess) return NRNERF_ERR_HIP;
-        if (I == 0) return NRNERF_OK;
-        if (bend) ge = bender_pass(z_fine, SF, bent_final, a->fine, 4);
-        if (ge != hipSuccess) return NRNERF_ERR_HIP;
-        const CompositeArgs gf = composite_args(/*final=*/true, raw_f);
-        ge = network_pass(m->gen_fine.prog, m->gen_fine, z_fine, SF, bend ? bent_final : nullptr, raw_f, a->raw, surface ? bent_final : nullptr, a->fine, 2,
-                          &gf, &fused_f);
-        if (ge != hipSuccess) return NRNERF_ERR_HIP;
-        if (!fused_f && timed(3, "composite_kernel", 0, 0, [&] { return launch_composite(gf, stream); }) != hipSuccess) return NRNERF_ERR_HIP;
-        return NRNERF_OK;
-    }
-
-    // ---- K0: coarse network
-    NetArgs na{};
-    na.rays = a->rays; na.ray_stride = a->ray_stride;
-    na.latents = a->latents; na.lat_stride = a->latent_stride;
-    na.z = zc; na.lindisp = a->lindisp; na.n_rays = N; na.S = S;
-    na.wstream = m->coarse.stream; na.bias = m->coarse.bias;
-    na.raw4 = raw_c;
-    na.raw_out = (I == 0) ? a->raw : nullptr;
-    na.raw_ch = m->coarse.output_ch;
-    na.bent4 = (I == 0) ? bent4 : (split ? bent_c : nullptr);
-    na.ex = sample_out(a->coarse);
-    na.knobs = kn;
-    // The coarse pass stays fused by default: measured on MI355X (round 2), bender kernel 1.56 ms + trunk-only coarse
-    // kernel 8.72 ms = 10.28 ms against 10.22 ms fused -- nothing is saved there, unlike in the fine pass where a third of
-    // the samples skips the bender.  NRNERF_RENDER_SPLIT_COARSE splits it as well (A/B).
-    const bool split_coarse_on = (a->flags & NRNERF_RENDER_SPLIT_COARSE) != 0;
-    // The 16x16x32 trunk-only kernel (nrnerf_net_x16.h) for the passes of the split path when the call wants no detail outputs.
-    // Per call (nrnerf_render_args::flags; the parity tests run the kernels side by side in one process): NRNERF_RENDER_NO_X16 = the
-    // 32x32x16 kernels of nrnerf_net_mb.h, NRNERF_RENDER_X16_FINE_ONLY = the fine pass only, default = the coarse pass too --
-    // stand-alone bender over the S coarse samples + 16x16x32 trunk instead of the fused-bender 32x32x16 kernel.
-    const int x16_mode = (a->flags & NRNERF_RENDER_NO_X16) ? 0 : ((a->flags & NRNERF_RENDER_X16_FINE_ONLY) ? 1 : 2);
-    const bool x16_coarse = split && x16_mode >= 2 && m->coarse_trunk_x16.stream && !a->detailed_output && !kn.detailed;
-    const bool split_coarse = split && (split_coarse_on || x16_coarse);
-    // Compositing fused into the FINAL pass' network kernel (north_star: "compositing fused into the ray loop"; the
-    // reference calls raw2outputs inline, train.py:943-950): the kernel variants without a fused bender -- the trunk-only fine
-    // pass of the split-bender path, every pass of a model without bender -- let each wave own whole rays, keep their raw
-    // outputs in LDS and composite them itself (nrnerf_composite_ray.h: the composite kernel's own code, so the same bits).
-    // The pass' raw array (16 B per sample written and read back) never exists and one launch goes.  The coarse pass of a
-    // hierarchical render keeps its composite kernel: sample_pdf and the merge follow it there.
-    // NRNERF_RENDER_UNFUSED_COMPOSITE keeps the separate launch (A/B and bit-identity tests).
-    const bool unfused_composite = (a->flags & NRNERF_RENDER_UNFUSED_COMPOSITE) != 0;
-    // (small batches keep the separate launch: a fused pass hands out whole GROUPS of rays -- 4 rays = 24 blocks at 192 samples --
-    //  where the plain mapping hands out 8-block tiles, so below one group per CU the plain mapping fills more of the chip)
-    auto enough_rays_to_fuse = [&](int pass_S) {
-        const int bpr = (pass_S + 31) / 32;
-        // rays per group = waves per workgroup x rays per wave: fp32 kernels 4 x 1; 16-bit two-blocks-per-wave kernels 4 x (1 or 2);
-        // 16-bit one-block-per-wave kernels (architecture 5) 8 x 1
-        const long long rays_per_group = (m->precision == NRNERF_PREC_F32) ? 4 : (m->arch_id == 5 ? 8 : ((bpr & 1) ? 8 : 4));
-        return (long long)N >= rays_per_group * m->num_cus;
-    };
-    const bool fuse_coarse_only = I == 0 && !m->has_bend && !unfused_composite && S <= 256 && enough_rays_to_fuse(S);
-    if (fuse_coarse_only) { na.fuse_on = 1; na.fuse = composite_args(/*final=*/true, nullptr); na.raw4 = nullptr; }
-    // ---- K1's arguments: coarse composite (+ sampling + merge when a fine pass follows)
-    CompositeArgs ca = composite_args(/*final=*/I == 0, raw_c);
-    if (I > 0 && split) { ca.split_bent_in = bent_c; ca.split_bent_out = bent4; ca.z_new = z_new; ca.rank_new = rank_new; }
-    // K1 inside K0 (north_star: "compositing fused into the ray loop"; train.py:889-920): on the split path's 16x16x32 coarse trunk a wave
-    // owns whole rays, so compositing, sample_pdf and the merge run as its epilogue (net_kernel_x16<.., SAMPLE>: composite_kernel's own
-    // code, same bits) and raw_c never reaches HBM.  NRNERF_RENDER_COARSE_EPILOGUE_ON / _OFF select per call; the default follows the
-    // A/B on one box.
-#ifndef NRN_COARSE_EPILOGUE_DEFAULT
-#define NRN_COARSE_EPILOGUE_DEFAULT 0
-#endif
-    const bool epilogue_wanted = (a->flags & NRNERF_RENDER_COARSE_EPILOGUE_OFF) ? false :
-                                 ((a->flags & NRNERF_RENDER_COARSE_EPILOGUE_ON) ? true : NRN_COARSE_EPILOGUE_DEFAULT != 0);
-    const bool fuse_coarse_epilogue = x16_coarse && epilogue_wanted && !unfused_composite && S <= x16_coarse_epilogue_max_samples() &&
-                                      (long long)N >= x16_rays_per_group(trunk_arch(m->arch_id), S) * m->num_cus;
-    if (fuse_coarse_epilogue) { na.fuse_on = 1; na.fuse = ca; na.fuse.raw4 = nullptr; na.raw4 = nullptr; }
-    hipError_t e;
-    if (split_coarse) {
-        // KBc: stand-alone bender over the S coarse samples, then the coarse trunk on the bent points
-        e = run_bender(5, zc, nullptr, S, S, bent_c, /*dynamic_shares=*/true);
-        if (e != hipSuccess) return NRNERF_ERR_HIP;
-        na.pts4 = bent_c; na.bent4 = nullptr;
-        if (x16_coarse) {
-            na.wstream = m->coarse_trunk_x16.stream; na.bias = m->coarse_trunk_x16.bias;
-            e = timed(0, (fuse_coarse_epilogue ? "net_kernel_x16 + fused compositing, sample_pdf, merge" : "net_kernel_x16"), (double)N * S * m->coarse_trunk_x16.algo_flops_per_sample, (double)N * S * m->coarse_trunk_x16.mfma_flops_per_sample,
-                      [&] { na.work_counter = trunk_counter(0); return launch_net_x16(m->precision, trunk_arch(m->arch_id), m->views, na, m->num_cus, stream); });
-        } else {
-            na.wstream = m->coarse_trunk.stream; na.bias = m->coarse_trunk.bias;
-            e = timed(0, "net_kernel (trunk only)", (double)N * S * m->coarse_trunk.algo_flops_per_sample, (double)N * S * m->coarse_trunk.mfma_flops_per_sample,
-                      [&] { return launch_net(m->precision, false, m->views, trunk_arch(m->arch_id), na, m->num_cus, stream); });
-        }
-    } else {
-        e = timed(0, (m->has_bend ? "net_kernel (fused bender)" : (fuse_coarse_only ? "net_kernel + fused compositing" : "net_kernel")), (double)N * S * m->coarse.algo_flops_per_sample, (double)N * S * m->coarse.mfma_flops_per_sample,
-                  [&] { return launch_net(m->precision, m->has_bend, m->views, m->exact ? 3 + m->arch_id : m->arch_id, na, m->num_cus, stream); });
-    }
-    if (e != hipSuccess) return NRNERF_ERR_HIP;
-    if (fuse_coarse_only) return NRNERF_OK;
-
-    // ---- K1: coarse composite (+ sampling), unless it ran as K0's epilogue
-    if (!fuse_coarse_epilogue)
-        e = timed(1, "composite_kernel", 0, 0, [&] { return launch_composite(ca, stream); });
-    if (e != hipSuccess) return NRNERF_ERR_HIP;
-    if (I == 0) return NRNERF_OK;
-
-    // ---- K2: fine network on the merged depths
-    NetArgs nf = na;
-    nf.fuse_on = 0; nf.fuse = CompositeArgs{};           // (the coarse pass' epilogue, if any, was its own)
-    nf.pts4 = nullptr;
-    nf.z = z_fine; nf.S = SF;
-    nf.raw4 = raw_f; nf.raw_out = a->raw; nf.raw_ch = m->fine.output_ch;
-    nf.ex = sample_out(a->fine);
-    // K3 inside K2 (see the comment on compositing in the final pass above) whenever K2 is a kernel without a fused bender
-    // the split path's trunk-only pass on the 16x16x32 kernel (nrnerf_net_x16.h) when the call wants no detail outputs
-    // (NRNERF_RENDER_NO_X16: the 32x32x16 kernel of nrnerf_net_mb.h)
-    // (read per call, like NRNERF_UNFUSED_COMPOSITE: the parity tests run both kernels in one process)
-    const bool x16 = split && x16_mode != 0 && m->fine_trunk_x16.stream && !a->detailed_output && !kn.detailed;
-    const long long x16_group = x16_rays_per_group(trunk_arch(m->arch_id), SF);          // (nrnerf_net_x16.hip: the kernel's own ray-group size)
-    const bool fuse_fine = (split || !m->has_bend) && !unfused_composite && SF <= 256 &&
-                           (x16 ? (long long)N >= x16_group * m->num_cus : enough_rays_to_fuse(SF));
-    if (fuse_fine) { nf.fuse_on = 1; nf.fuse = composite_args(/*final=*/true, nullptr); nf.raw4 = nullptr; }
-    if (split) {
-        // KB: only the I importance samples go through the bender; the coarse samples' bent points are already in place
-        e = run_bender(4, z_new, rank_new, I, SF, bent4, /*dynamic_shares=*/true);
-        if (e != hipSuccess) return NRNERF_ERR_HIP;
-        // K2: trunk + head on ready-made points (compiled architecture 0 without bender)
-        nf.pts4 = bent4; nf.bent4 = nullptr;
-        if (x16) {
-            nf.wstream = m->fine_trunk_x16.stream; nf.bias = m->fine_trunk_x16.bias;
-            e = timed(2, (fuse_fine ? "net_kernel_x16 + fused compositing" : "net_kernel_x16"), (double)N * SF * m->fine_trunk_x16.algo_flops_per_sample, (double)N * SF * m->fine_trunk_x16.mfma_flops_per_sample,
-                      [&] { nf.work_counter = trunk_counter(1); return launch_net_x16(m->precision, trunk_arch(m->arch_id), m->views, nf, m->num_cus, stream); });
-        } else {
-            nf.wstream = m->fine_trunk.stream; nf.bias = m->fine_trunk.bias;
-            e = timed(2, (fuse_fine ? "net_kernel (trunk only) + fused compositing" : "net_kernel (trunk only)"), (double)N * SF * m->fine_trunk.algo_flops_per_sample, (double)N * SF * m->fine_trunk.mfma_flops_per_sample,
-                      [&] { return launch_net(m->precision, false, m->views, trunk_arch(m->arch_id), nf, m->num_cus, stream); });
-        }
-    } else {
-        nf.wstream = m->fine.stream; nf.bias = m->fine.bias;
-        nf.bent4 = bent4;
-        e = timed(2, (m->has_bend ? "net_kernel (fused bender)" : (fuse_fine ? "net_kernel + fused compositing" : "net_kernel")), (double)N * SF * m->fine.algo_flops_per_sample, (double)N * SF * m->fine.mfma_flops_per_sample,
-                  [&] { return launch_net(m->precision, m->has_bend, m->views, m->exact ? 3 + m->arch_id : m->arch_id, nf, m->num_cus, stream); });
-    }
-    if (e != hipSuccess) return NRNERF_ERR_HIP;
-
-    if (fuse_fine) return NRNERF_OK;
-
-    // ---- K3: fine composite
-    const CompositeArgs cf = composite_args(/*final=*/true, raw_f);
-    e = timed(3, "composite_kernel", 0, 0, [&] { return launch_composite(cf, stream); });
-    if (e != hipSuccess) return NRNERF_ERR_HIP;
-    return NRNERF_OK;
+    const int rc = call.run_pass(plan.coarse);
+    return (rc == NRNERF_OK && plan.fine.exists) ? call.run_pass(plan.fine) : rc;
 } NRN_CATCH
 
 int nrnerf_generate_rays(const nrnerf_camera* cam, float near_plane, float far_plane, float* rays_out,

@@ -1647,3 +1647,119 @@ def test_f16_mode_with_the_single_product_bender_is_at_least_as_accurate_as_bf16
     # (no absolute bar here: this is the numerical stress scene -- sigma logits ~ N(-2, 6^2) -- on which "bf16" mode sits at 34-37 dB; the
     #  stated >= 40 dB / <= 0.1 dB bar is held on the fitted checkpoints, tests/test_fitted_checkpoint.py)
     assert psnr(f16["rgb0"], ref32["rgb0"]) >= psnr(bf16["rgb0"], ref32["rgb0"])
+
+
+_HEADLINE = dict()
+_GENERIC = dict(N_importance=128, netdepth=6, netwidth=192, netwidth_fine=320, multires=8)
+# id -> (SceneConfig arguments, precision, NRNERF_* switches of the call, detailed_output)
+_ROUTE_CASES = {
+    "headline":                 (_HEADLINE, "bf16", {}, False),
+    "headline_f16":             (_HEADLINE, "f16", {}, False),
+    "headline_f32":             (_HEADLINE, "f32", {}, False),
+    "coarse_only":              (dict(N_importance=0), "bf16", {}, False),
+    "no_bender":                (dict(ray_bending=False), "bf16", {}, False),
+    "no_bender_coarse_only":    (dict(ray_bending=False, N_importance=0), "bf16", {}, False),
+    "viewdirs":                 (dict(N_importance=64, use_viewdirs=True), "bf16", {}, False),
+    "exact_viewdirs":           (dict(N_importance=64, use_viewdirs=True, approx_nonrigid_viewdirs=False), "bf16", {}, False),
+    "narrow_128":               (dict(N_importance=64, netwidth=128), "bf16", {}, False),
+    "deep_bender":              (dict(N_importance=64, bend_depth=7), "bf16", {}, False),
+    "over_256_samples":         (dict(N_samples=160, N_importance=160), "bf16", {}, False),
+    "detailed_output":          (_HEADLINE, "bf16", {}, True),
+    "x16_0":                    (_HEADLINE, "bf16", {"NRNERF_X16": "0"}, False),
+    "x16_1":                    (_HEADLINE, "bf16", {"NRNERF_X16": "1"}, False),
+    "x16_2":                    (_HEADLINE, "bf16", {"NRNERF_X16": "2"}, False),
+    "x16_bender_0":             (_HEADLINE, "bf16", {"NRNERF_X16_BENDER": "0"}, False),
+    "fused_fine_bender":        (_HEADLINE, "bf16", {"NRNERF_FUSED_FINE_BENDER": "1"}, False),
+    "unfused_composite":        (_HEADLINE, "bf16", {"NRNERF_UNFUSED_COMPOSITE": "1"}, False),
+    "split_coarse":             (_HEADLINE, "bf16", {"NRNERF_SPLIT_COARSE": "1"}, False),
+    "split_coarse_x16_0":       (_HEADLINE, "bf16", {"NRNERF_SPLIT_COARSE": "1", "NRNERF_X16": "0"}, False),
+    "coarse_epilogue_0":        (_HEADLINE, "bf16", {"NRNERF_FUSED_COARSE_EPILOGUE": "0"}, False),
+    "coarse_epilogue_1":        (_HEADLINE, "bf16", {"NRNERF_FUSED_COARSE_EPILOGUE": "1"}, False),
+    "fixed_shares":             (_HEADLINE, "bf16", {"NRNERF_FIXED_SHARES": "1"}, False),
+    "generic_w192_320":         (_GENERIC, "bf16", {}, False),
+    "generic_w192_320_f16":     (_GENERIC, "f16", {}, False),
+    "generic_w192_320_f32":     (_GENERIC, "f32", {}, False),
+    "generic_viewdirs":         (dict(N_importance=64, netwidth=160, use_viewdirs=True), "bf16", {}, False),
+    "generic_coarse_only":      (dict(N_importance=0, netwidth=192), "bf16", {}, False),
+    "generic_exact_viewdirs":   (dict(N_importance=64, netdepth=6, netwidth=192, netwidth_fine=160, skips=(2,), use_viewdirs=True,
+                                      approx_nonrigid_viewdirs=False), "bf16", {}, False),
+    "generic_own_bender":       (dict(N_importance=64, netwidth=192, bend_hidden=96), "bf16", {}, False),
+    "generic_x16_0":            (_GENERIC, "bf16", {"NRNERF_X16": "0"}, False),
+    "generic_x16_bender_0":     (_GENERIC, "bf16", {"NRNERF_X16_BENDER": "0"}, False),
+    "generic_unfused_composite": (_GENERIC, "bf16", {"NRNERF_UNFUSED_COMPOSITE": "1"}, False),
+    "generic_detailed_output":  (_GENERIC, "bf16", {}, True),
+}
+# id -> (route of the small batch, route of the large batch); a route: per profile slot (net_coarse, composite_sample_coarse, net_fine,
+# composite_fine, bend_fine, bend_coarse) the name of the one launch, "" for none
+_ROUTES = {
+    "headline": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('net_kernel_x16', 'composite_kernel', 'net_kernel_x16 + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "headline_f16": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('net_kernel_x16', 'composite_kernel', 'net_kernel_x16 + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "headline_f32": (('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (trunk only)', 'composite_kernel', 'bend_kernel', ''), ('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (trunk only) + fused compositing', '', 'bend_kernel', '')),
+    "coarse_only": (('net_kernel (fused bender)', 'composite_kernel', '', '', '', ''), ('net_kernel (fused bender)', 'composite_kernel', '', '', '', '')),
+    "no_bender": (('net_kernel', 'composite_kernel', 'net_kernel', 'composite_kernel', '', ''), ('net_kernel', 'composite_kernel', 'net_kernel + fused compositing', '', '', '')),
+    "no_bender_coarse_only": (('net_kernel', 'composite_kernel', '', '', '', ''), ('net_kernel + fused compositing', '', '', '', '', '')),
+    "viewdirs": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('net_kernel_x16', 'composite_kernel', 'net_kernel_x16 + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "exact_viewdirs": (('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (fused bender)', 'composite_kernel', '', ''), ('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (fused bender)', 'composite_kernel', '', '')),
+    "narrow_128": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('net_kernel_x16', 'composite_kernel', 'net_kernel_x16 + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "deep_bender": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('net_kernel_x16', 'composite_kernel', 'net_kernel_x16 + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "over_256_samples": (('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (fused bender)', 'composite_kernel', '', ''), ('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (fused bender)', 'composite_kernel', '', '')),
+    "detailed_output": (('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (fused bender)', 'composite_kernel', '', ''), ('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (fused bender)', 'composite_kernel', '', '')),
+    "x16_0": (('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (trunk only)', 'composite_kernel', 'bend_kernel', ''), ('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (trunk only) + fused compositing', '', 'bend_kernel', '')),
+    "x16_1": (('net_kernel (fused bender)', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', ''), ('net_kernel (fused bender)', 'composite_kernel', 'net_kernel_x16 + fused compositing', '', 'bend_kernel_x16', '')),
+    "x16_2": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('net_kernel_x16', 'composite_kernel', 'net_kernel_x16 + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "x16_bender_0": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel', 'bend_kernel'), ('net_kernel_x16', 'composite_kernel', 'net_kernel_x16 + fused compositing', '', 'bend_kernel', 'bend_kernel')),
+    "fused_fine_bender": (('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (fused bender)', 'composite_kernel', '', ''), ('net_kernel (fused bender)', 'composite_kernel', 'net_kernel (fused bender)', 'composite_kernel', '', '')),
+    "unfused_composite": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "split_coarse": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('net_kernel_x16', 'composite_kernel', 'net_kernel_x16 + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "split_coarse_x16_0": (('net_kernel (trunk only)', 'composite_kernel', 'net_kernel (trunk only)', 'composite_kernel', 'bend_kernel', 'bend_kernel'), ('net_kernel (trunk only)', 'composite_kernel', 'net_kernel (trunk only) + fused compositing', '', 'bend_kernel', 'bend_kernel')),
+    "coarse_epilogue_0": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('net_kernel_x16', 'composite_kernel', 'net_kernel_x16 + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "coarse_epilogue_1": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('net_kernel_x16 + fused compositing, sample_pdf, merge', '', 'net_kernel_x16 + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "fixed_shares": (('net_kernel_x16', 'composite_kernel', 'net_kernel_x16', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('net_kernel_x16', 'composite_kernel', 'net_kernel_x16 + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "generic_w192_320": (('gx16_kernel', 'composite_kernel', 'gx16_kernel', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('gx16_kernel', 'composite_kernel', 'gx16_kernel + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "generic_w192_320_f16": (('gx16_kernel', 'composite_kernel', 'gx16_kernel', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('gx16_kernel', 'composite_kernel', 'gx16_kernel + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "generic_w192_320_f32": (('gen_kernel', 'composite_kernel', 'gen_kernel', 'composite_kernel', 'bend_kernel', 'bend_kernel'), ('gen_kernel', 'composite_kernel', 'gen_kernel', 'composite_kernel', 'bend_kernel', 'bend_kernel')),
+    "generic_viewdirs": (('gx16_kernel', 'composite_kernel', 'gx16_kernel', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('gx16_kernel', 'composite_kernel', 'gx16_kernel + fused compositing', '', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "generic_coarse_only": (('gx16_kernel', 'composite_kernel', '', '', '', 'bend_kernel_x16'), ('gx16_kernel + fused compositing', '', '', '', '', 'bend_kernel_x16')),
+    "generic_exact_viewdirs": (('gen_kernel (exact Jacobian directions)', 'composite_kernel', 'gen_kernel (exact Jacobian directions)', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('gen_kernel (exact Jacobian directions)', 'composite_kernel', 'gen_kernel (exact Jacobian directions)', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "generic_x16_0": (('gen_kernel', 'composite_kernel', 'gen_kernel', 'composite_kernel', 'bend_kernel', 'bend_kernel'), ('gen_kernel', 'composite_kernel', 'gen_kernel', 'composite_kernel', 'bend_kernel', 'bend_kernel')),
+    "generic_x16_bender_0": (('gx16_kernel', 'composite_kernel', 'gx16_kernel', 'composite_kernel', 'bend_kernel', 'bend_kernel'), ('gx16_kernel', 'composite_kernel', 'gx16_kernel + fused compositing', '', 'bend_kernel', 'bend_kernel')),
+    "generic_unfused_composite": (('gx16_kernel', 'composite_kernel', 'gx16_kernel', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16'), ('gx16_kernel', 'composite_kernel', 'gx16_kernel', 'composite_kernel', 'bend_kernel_x16', 'bend_kernel_x16')),
+    "generic_detailed_output": (('gen_kernel', 'composite_kernel', 'gen_kernel', 'composite_kernel', 'gen_kernel (bender program)', 'gen_kernel (bender program)'), ('gen_kernel', 'composite_kernel', 'gen_kernel', 'composite_kernel', 'gen_kernel (bender program)', 'gen_kernel (bender program)')),
+    "generic_own_bender": (('gx16_kernel', 'composite_kernel', 'gx16_kernel', 'composite_kernel', 'gen_kernel (bender program)', 'gen_kernel (bender program)'), ('gx16_kernel', 'composite_kernel', 'gx16_kernel + fused compositing', '', 'gen_kernel (bender program)', 'gen_kernel (bender program)')),
+}
+
+
+def _route_of(model, cfg, n, env, detailed):
+    """The kernels one render of n rays takes, as the library's profile reports them: per slot (_lib.KERNEL_NAMES order) the display name
+    of the launch, "" for a slot without one."""
+    rays, latents = make_rays(n, 11, cfg)
+    with contextlib.ExitStack() as stack:
+        for k, v in env.items():
+            stack.enter_context(_setenv(k, v))
+        model.profile_begin()
+        with torch.no_grad():
+            model.render(rays.to(DEV), latents.to(DEV), cfg.N_samples, cfg.N_importance, detailed_output=detailed)
+        torch.cuda.synchronize()
+        prof = model.profile_end()
+    for slot in prof.values():
+        assert slot["launches"] == (1 if slot["kernel"] else 0), prof
+    return tuple(slot["kernel"] for slot in prof.values())
+
+
+@pytest.mark.parametrize("case", list(_ROUTE_CASES))
+def test_every_call_takes_the_kernels_the_route_table_says(case):
+    """Which kernels a call takes is decided in one place (plan_render, csrc/nrnerf_api.cpp); this pins the decision to a literal table,
+    recorded from the library as it was before that function existed.  Per case two renders between profile_begin and profile_end: a small
+    batch -- two rays per CU, below one ray group per CU (a group is at least four rays), where the fused epilogues decline -- and a large
+    one -- 48 rays per CU, above the largest group (8 waves x 4 rays).  For all six profile slots the kernel name and the launch count
+    (one launch where there is a name, none where there is not) must be the table's.  The CU count is the device's multiprocessor count,
+    which is what the library sizes its thresholds from."""
+    cfg_kw, precision, env, detailed = _ROUTE_CASES[case]
+    cfg = SceneConfig(**cfg_kw)
+    rb, coarse, fine = build_modules(make_scene(cfg, 4), device=DEV)
+    R.set_precision(precision)
+    model = R.get_model(coarse, fine if cfg.N_importance > 0 else None)
+    cus = torch.cuda.get_device_properties(model.device).multi_processor_count
+    got = tuple(_route_of(model, cfg, n, env, detailed) for n in (2 * cus, 48 * cus))
+    print(f'    "{case}": {got!r},')
+    assert got == _ROUTES[case], (case, got, _ROUTES[case])
