@@ -320,7 +320,7 @@ class Model:
         desc, keep = build_model_desc(network_fn, network_fine, self.precision, self.device.index, self.flags)
         self.has_bender = bool(desc.bender)
         # nrnerf_bender_* / nrnerf_bender_divergence_* are available (the library's own rule: training_eligible in
-        # csrc/nrnerf_api.cpp): a bender, not an f16 handle
+        # csrc/nrnerf_pack.cpp): a bender, not an f16 handle
         self.trains_bender = bool(desc.bender) and self.precision != "f16"
         self.needs_latents = self.has_bender or bool(desc.coarse.contents.time_conditioned)
         self.latent_size = desc.bender.contents.latent_size if self.has_bender else \

@@ -353,7 +353,7 @@ def test_bf16_gradients_point_the_same_way(width, detailed, views, S, I):
 @pytest.mark.parametrize("bender", [False, "torch_ops", "native"], ids=["no_bender", "torch_ops_bender", "native_bender"])
 def test_generic_training_sees_an_optimiser_step_in_forward_and_backward_weights(bender):
     """A non-compiled architecture keeps TWO images of every trunk weight on the device -- the forward program's and the transposed
-    one of the backward-data program (csrc/nrnerf_api.cpp::gen_pack_mlp_bwd) -- and an optimiser step must reach both through the
+    one of the backward-data program (csrc/nrnerf_pack.cpp::gen_pack_mlp_bwd) -- and an optimiser step must reach both through the
     device-side re-pack (nrnerf_model_update_device: the source maps of the transposed fragments).  Gradients after a large step
     against the oracle's autograd on the stepped weights, fp32 mode, 2e-3 of each tensor's scale as in the test above (stale
     transposed weights would leave d_pre, hence every gradient but the head's, at the old weights' values).  ``native_bender``: the bender's
