@@ -5,7 +5,7 @@
  * Boundary being replaced (reference facebookresearch/nonrigid_nerf):
  *   batchify_rays          train.py:108-137   (chunk loop; subsumed: one nrnerf_render call takes any n_rays)
  *   render_rays            train.py:792-980   (whole per-ray algorithm)
- *     run_network/batchify train.py:57-105, 27-54
+ *     run_network/batchify train.py:57-105, 27-54   (also on its own: nrnerf_query, the network_query_fn of train.py:633-649)
  *     Embedder.embed       run_nerf_helpers.py:120-168
  *     NeRF.forward         run_nerf_helpers.py:240-314
  *     ray_bending.forward  run_nerf_helpers.py:507-584
@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define NRNERF_ABI_VERSION 9
+#define NRNERF_ABI_VERSION 10
 /* samples per ray and pass: nrnerf_render and the training entry points (the split fine bender -- nrnerf_merge_rows,
  * nrnerf_composite_args.rank_new -- up to 256 merged samples: 8-bit ranks) */
 #define NRNERF_MAX_SAMPLES 1024
@@ -853,6 +853,56 @@ int nrnerf_image_metrics(const nrnerf_metrics_args* args, void* hip_stream);
  * out_rgb [n_pixels,3] = jet(clip(10 * mean_c std)), std the population deviation (ddof 0) sqrt(max(sum_sq / F - (sum / F)^2, 0)). */
 int nrnerf_stability_accumulate(const float* rgb, int64_t n_values, double* sum, double* sum_sq, void* hip_stream);
 int nrnerf_stability_finish(const double* sum, const double* sum_sq, int32_t n_frames, int64_t n_pixels, uint8_t* out_rgb, void* hip_stream);
+
+/* ---- ABI 10: the radiance field itself, on caller-given points.
+ *
+ * nrnerf_query is the reference's network_query_fn (create_nerf's render_kwargs["network_query_fn"], train.py:633-649 -> run_network,
+ * train.py:57-105): NeRF.forward, ray bender included, on ANY [n_rows, n_samples, 3] array of points -- one pass, no compositing.  A ROW
+ * is what run_network calls a ray: the latent code and the view direction are per row, and with a view-dependent head behind a bender the
+ * finite-difference direction of a sample (rnh:339-351) is taken along the row (the first sample copies the second; n_samples == 1 is
+ * then NRNERF_ERR_INVALID: there is no neighbour).  Route: the point-source variant of the stand-alone bender (a compiled bender shape)
+ * writes bent points to the workspace, the trunk-only network kernel a render pass would take runs on them and writes `raw`; without a
+ * bender the points are packed to rows of four floats and the trunk-only kernel runs alone.  With a view-dependent head and NO bender
+ * the directions are `viewdirs` (train.py:73-76).  Device pointers only, asynchronous on the stream, allocates nothing.
+ * NRNERF_ERR_UNSUPPORTED (no kernel is written for these; the Python boundary hands the call to the reference when it has it): exact
+ * (Jacobian) view directions; a bender that is not one of the two compiled shapes (5 x 64, 7 x 64; latent 32, rigidity 3 x 32); a
+ * compiled architecture without a trunk-only plan; 2^31 or more sample blocks.
+ * flags: NRNERF_RENDER_NO_X16, NRNERF_RENDER_BENDER_32X32 and NRNERF_RENDER_FIXED_SHARES as in nrnerf_render; any other bit is
+ * NRNERF_ERR_INVALID.  The launches record into the handle's profile (nrnerf_profile_begin / _end): slot 0 / 2 the network kernel of
+ * which = 0 / 1, slot 5 / 4 the bender. */
+typedef struct nrnerf_query_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_query_args) */
+    int32_t which;              /* 0 = network_fn, 1 = network_fine (the coarse network when the model has no fine one) */
+    int32_t n_rows;             /* N >= 0 */
+    int32_t n_samples;          /* S: 1 <= S <= NRNERF_MAX_SAMPLES */
+    const float* points;        /* [N, S, point_stride] */
+    int32_t point_stride;       /* floats per point, >= 3 (4 and a 16-byte aligned base: 16-byte loads) */
+    int32_t latent_stride;      /* floats between the rows of `latents`; 0 = one code for the call */
+    const float* latents;       /* [N, latent_size]; may be NULL when the model takes no latent code */
+    const float* viewdirs;      /* [N, 3] unit directions (train.py:73-76): read by a view-dependent head WITHOUT a bender; else may be NULL */
+    int32_t has_rigidity_cutoff;   float rigidity_cutoff;     /* the knobs of nrnerf_render_args */
+    int32_t has_test_time_scaling; float test_time_scaling;
+    int32_t has_removal_threshold; float removal_threshold;   /* honoured only under detailed_output (rnh:308-311) */
+    int32_t detailed_output;
+    uint32_t flags;             /* bits of nrnerf_render_flags, see above */
+    int32_t raw_ch;             /* floats per row of `raw`: the network's output_ch (4 with a view-dependent head), or 4 */
+    float* raw;                 /* out [N, S, raw_ch] */
+    nrnerf_sample_outputs details;  /* initial_input_pts (a copy of the input), unmasked / masked offsets, input_pts, rigidity_mask; any may
+                                       be NULL.  visibility_weights / opacity_alpha belong to compositing and must be NULL.  Without a
+                                       bender only the two point tensors are legal (NRNERF_ERR_INVALID otherwise) */
+    void* workspace;            /* >= nrnerf_query_workspace_bytes(), 256-byte aligned */
+    size_t workspace_bytes;
+} nrnerf_query_args;
+size_t nrnerf_query_workspace_bytes(const nrnerf_model* model, int32_t which, int32_t n_rows, int32_t n_samples);
+int nrnerf_query(const nrnerf_model* model, const nrnerf_query_args* args, void* hip_stream);
+
+/* Rows [first_row, first_row + n_rows) of a regular, vertex-centred grid of gx x gy x gz points as rows of four floats (w = 0): row =
+ * iz * gy + iy, sample = ix; p_c = min_c + i_c * ((max_c - min_c) / (g_c - 1)), and g_c == 1 gives min_c.  pts4 [n_rows, gx, 4]. */
+int nrnerf_grid_points(const float min_point[3], const float max_point[3], int32_t gx, int32_t gy, int32_t gz, int64_t first_row,
+                       int32_t n_rows, float* pts4, void* hip_stream);
+/* raw [n, raw_ch >= 4] -> sigma [n] = relu(raw[.,3]) (train.py:740-741) and rgb8 [n, 3] = to8b(sigmoid(raw[., 0..2])) with the reference's
+ * truncating to8b ((255 * clip(x, 0, 1)).astype(uint8)).  Either output may be NULL. */
+int nrnerf_field_from_raw(const float* raw, int32_t raw_ch, int64_t n, float* sigma, uint8_t* rgb8, void* hip_stream);
 
 /* Host-only packing (no device needed): writes the MFMA-fragment weight stream + unit table + bias
  * table of one pass exactly as nrnerf_model_create uploads them.  which: 0 = coarse, 1 = fine, 2 = fine without the

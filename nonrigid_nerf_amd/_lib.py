@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # NRNERF_LIB selects an alternative build of the same library (tuning experiments, see csrc/Makefile)
 LIB_PATH = os.environ.get("NRNERF_LIB") or os.path.join(_HERE, "lib", "libnrnerf_hip.so")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 MAX_SAMPLES = 1024        # NRNERF_MAX_SAMPLES (include/nrnerf.h): per ray and pass of nrnerf_render; training: 256
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP, ERR_WORKSPACE, ERR_NOMEM, ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6
 PRECISIONS = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "f16": 2, "fp16": 2, "float16": 2}
@@ -311,6 +311,22 @@ class MetricsArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+class QueryArgs(C.Structure):
+    """nrnerf_query_args (ABI 10): the networks on caller-given points, one pass, no compositing."""
+    _fields_ = [("struct_size", C.c_uint32), ("which", C.c_int32), ("n_rows", C.c_int32), ("n_samples", C.c_int32),
+                ("points", C.c_void_p), ("point_stride", C.c_int32), ("latent_stride", C.c_int32),
+                ("latents", C.c_void_p), ("viewdirs", C.c_void_p),
+                ("has_rigidity_cutoff", C.c_int32), ("rigidity_cutoff", C.c_float),
+                ("has_test_time_scaling", C.c_int32), ("test_time_scaling", C.c_float),
+                ("has_removal_threshold", C.c_int32), ("removal_threshold", C.c_float),
+                ("detailed_output", C.c_int32), ("flags", C.c_uint32), ("raw_ch", C.c_int32),
+                ("raw", C.c_void_p), ("details", SampleOutputs),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+QUERY_FLAGS = RENDER_NO_X16 | RENDER_BENDER_32X32 | RENDER_FIXED_SHARES      # the render flags nrnerf_query honours; any other bit: INVALID
+
+
 EXPORTS = {
     "nrnerf_abi_version": (C.c_int, []),
     "nrnerf_strerror": (C.c_char_p, [C.c_int]),
@@ -336,6 +352,10 @@ EXPORTS = {
     "nrnerf_code_gradients": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "nrnerf_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
     "nrnerf_render": (C.c_int, [C.c_void_p, C.POINTER(RenderArgs), C.c_void_p]),
+    "nrnerf_query_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "nrnerf_query": (C.c_int, [C.c_void_p, C.POINTER(QueryArgs), C.c_void_p]),
+    "nrnerf_grid_points": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "nrnerf_field_from_raw": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "nrnerf_generate_rays": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
     "nrnerf_sample_depths": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "nrnerf_sample_depths_points": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

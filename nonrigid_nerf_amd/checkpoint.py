@@ -133,7 +133,8 @@ def load_checkpoint(path_or_dict, N_samples: int = 64, N_importance: int | None 
     if latents is not None and device is not None:
         latents = latents.to(device)
 
-    kwargs = {"network_query_fn": None, "perturb": False, "N_importance": N_importance, "network_fine": fine,
+    from . import render as _render          # (the library loads with the first handle, not with this import)
+    kwargs = {"network_query_fn": _render.network_query_fn, "perturb": False, "N_importance": N_importance, "network_fine": fine,
               "N_samples": N_samples, "network_fn": coarse, "ray_bender": rb, "use_viewdirs": arch["use_viewdirs"],
               "white_bkgd": False, "raw_noise_std": 0.0, "ndc": False, "lindisp": False}
     rest = {k: v for k, v in ck.items() if k not in ("network_fn_state_dict", "network_fine_state_dict",

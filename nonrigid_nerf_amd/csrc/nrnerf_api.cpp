@@ -7,6 +7,8 @@
 //   K1  composite (+ sample_pdf + merge + z_std when I > 0)               -> rgb0/disp0/acc0 or final; z_fine [N,S+I]
 //   K2  network kernel, fine weights, z = z_fine                          -> raw_f [N,S+I,4]
 //   K3  composite                                                         -> rgb/disp/acc
+// nrnerf_query (the reference's network_query_fn, train.py:57-105, 633-649) is ONE pass of that sequence on caller-given points, without
+// compositing: plan_query / QueryCall below, on RenderCall's network step.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -19,6 +21,8 @@
 #include "nrnerf_aux.h"
 #include "nrnerf_x16_api.h"
 #include "nrnerf_plan.h"
+#include "nrnerf_bend_points.h"
+#include "nrnerf_field.h"
 
 using namespace nrn;
 
@@ -381,7 +385,20 @@ struct RenderCall {
     unsigned* counters;            // one counter per stand-alone bender launch of the call and per 16x16x32 trunk launch, 64 bytes apart
     bool counters_zeroed = false;
     const float* zc = nullptr;     // explicit coarse depths (stratified jitter), or null: the coarse spacing
+    const float* given_pts = nullptr;      // nrnerf_query without a bender: the pass' ready-made points [N, S, 4] (else: what a bender step wrote)
 
+    // nrnerf_query: one pass on a workspace of its own -- the pass' raw rows, its points, the work counters (`a`: the call as a render call)
+    RenderCall(const nrnerf_model* m_, const nrnerf_render_args* a_, const RenderPlan& plan_, hipStream_t stream_, float* raw4, float* pts4, unsigned* counters_)
+        : m(m_), a(a_), plan(plan_), stream(stream_) {
+        raw_c = raw_f = raw4; bent4_ws = bent_c = pts4; counters = counters_;
+        z_fine = z_coarse = z_new = jdirs = nullptr; rank_new = nullptr;
+        kn.has_cutoff = a->has_rigidity_cutoff; kn.cutoff = a->rigidity_cutoff;
+        kn.has_scaling = a->has_test_time_scaling; kn.scaling = a->test_time_scaling;
+        kn.has_removal = a->has_removal_threshold; kn.removal = a->removal_threshold;
+        kn.detailed = a->detailed_output;
+        std::lock_guard<std::mutex> g(m->prof_mu);
+        prof = m->prof_on;
+    }
     RenderCall(const nrnerf_model* m_, const nrnerf_render_args* a_, const RenderPlan& plan_, const WorkspaceLayout& lay, hipStream_t stream_)
         : m(m_), a(a_), plan(plan_), stream(stream_) {
         void* const ws = a->workspace;
@@ -489,7 +506,7 @@ struct RenderCall {
         const bool fused = p.comp != CompStep::Launch;
         const ImageDev& im = m->img[p.image];
         const nrnerf_sample_outputs& so = outputs_of(p);
-        const float* const pts = (p.bend == BendStep::Compiled || p.bend == BendStep::Program) ? points_of(p) : nullptr;      // ready-made points
+        const float* const pts = given_pts ? given_pts : ((p.bend == BendStep::Compiled || p.bend == BendStep::Program) ? points_of(p) : nullptr);      // ready-made points
         // without them the kernel reports the points it evaluates where a later step reads them: the surface reduction, the split fine pass
         float* const pts_out = (!pts && (p.final ? plan.surface : plan.split)) ? points_of(p) : nullptr;
         float* const raw4 = fused ? nullptr : raw_of(p);
@@ -524,7 +541,7 @@ struct RenderCall {
             GenArgs g = im.prog;
             g.rays = a->rays; g.ray_stride = a->ray_stride; g.latents = a->latents; g.lat_stride = a->latent_stride;
             g.z = depths_of(p); g.lindisp = a->lindisp; g.n_rays = N; g.S = p.S;
-            g.pts4 = pts; g.dirs_from_pts = (pts && m->views) ? 1 : 0;
+            g.pts4 = pts; g.dirs_from_pts = (pts && m->views && m->has_bend) ? 1 : 0;      // (ready-made points without a bender -- nrnerf_query -- keep the rays' directions)
             g.wstream = im.stream; g.bias = im.bias;
             g.raw4 = raw4; g.raw_out = raw_out; g.raw_ch = im.output_ch;
             g.bent4 = pts ? const_cast<float*>(pts) : pts_out;          // with a bender: read (removal knob); without: written (points of the pass)
@@ -597,6 +614,195 @@ int nrnerf_render(const nrnerf_model* m, const nrnerf_render_args* a, void* hip_
     }
     const int rc = call.run_pass(plan.coarse);
     return (rc == NRNERF_OK && plan.fine.exists) ? call.run_pass(plan.fine) : rc;
+} NRN_CATCH
+
+}  // extern "C"
+namespace {
+// ---- nrnerf_query: the networks on caller-given points (run_network, train.py:57-105).  plan_query decides (no HIP call), QueryCall launches:
+// a packing step, a bender step (the point-source stand-alone bender), RenderCall's network step, the detail tensors.
+constexpr unsigned QUERY_FLAGS = NRNERF_RENDER_NO_X16 | NRNERF_RENDER_BENDER_32X32 | NRNERF_RENDER_FIXED_SHARES;
+struct QueryPlan {
+    int status = NRNERF_OK;
+    PassPlan pass;                 // bend: None or Compiled; net: NetX16 / NetTrunk / Gx16 / Gen; comp unused (nothing is composited)
+    bool bend_x16 = false;
+    // A compiled view-dependent head WITHOUT a bender: its trunk-only kernels take the direction of ready-made points from the points' finite
+    // differences (the split path's contract), which is not what run_network computes here (the row's viewdirs, train.py:73-76).  Such a query runs
+    // on ray records instead -- one record per POINT (origin = the point, direction 0, near = far = 0, the row's unit direction), a "ray" of one
+    // sample at depth 0: the kernel's o + d z is the point itself.
+    bool per_point = false;
+    bool point_latents = false;    // ... with the row's latent code copied per point (time-conditioned baseline)
+};
+// the workspace of a query: 256-byte aligned slots, as WorkspaceLayout
+struct QueryLayout {
+    size_t raw4, pts4, records, point_records, point_latents, counters, total = 0;
+    QueryLayout(const nrnerf_model& m, const QueryPlan& q, int n_rows, int n_samples) {
+        const size_t N = (size_t)n_rows, M = N * (size_t)n_samples;
+        auto slot = [&](size_t bytes, bool present = true) {
+            const size_t at = total;
+            if (present) total += align_up(bytes, 256);
+            return at;
+        };
+        raw4 = slot(M * 4 * sizeof(float));                          // rgb + sigma rows of the network kernel
+        pts4 = slot(M * 4 * sizeof(float));                          // the points of the pass: packed input, or bent point + rigidity
+        records = slot(N * 11 * sizeof(float));                      // a ray record per row: zeros + the unit direction
+        point_records = slot(M * 11 * sizeof(float), q.per_point);
+        point_latents = slot(M * (size_t)m.latent_size * sizeof(float), q.point_latents);
+        counters = slot(BEND_COUNTER_BYTES);
+    }
+};
+
+QueryPlan plan_query(const nrnerf_model& m, int which, int N, int S, unsigned flags) {
+    QueryPlan q;
+    PassPlan& p = q.pass;
+    auto flag = [&](unsigned f) { return (flags & f) != 0; };
+    const bool dynamic = !flag(NRNERF_RENDER_FIXED_SHARES);
+    p.exists = true; p.final = true; p.which = which; p.S = S;
+    p.net_slot = 2 * which; p.bend_slot = 5 - which;
+    const bool own = which && !m.fine_is_coarse;            // (one network for both passes: `which` = 1 runs on the coarse images)
+    if (m.exact) { q.status = NRNERF_ERR_UNSUPPORTED; return q; }       // exact Jacobian directions: fused / divergence kernels only
+    if ((long long)N * S >= (1ll << 31) || !block_index_fits(N, S)) { q.status = NRNERF_ERR_UNSUPPORTED; return q; }
+    if (m.has_bend) {
+        // the point-source stand-alone bender: a compiled shape with its image in the handle
+        if (!(m.generic ? m.gen_compiled_bender >= 0 : m.split_ok != 0) || !m.bend_only.stream) { q.status = NRNERF_ERR_UNSUPPORTED; return q; }
+        p.bend = BendStep::Compiled; p.bend_n = p.bend_stride = S;
+        q.bend_x16 = m.bend_x16.stream && !flag(NRNERF_RENDER_BENDER_32X32 | NRNERF_RENDER_NO_X16);
+        p.bend_dynamic = q.bend_x16 && dynamic && m.num_cus <= BEND_COUNTERS_PER_LAUNCH;
+    }
+    const bool rows_give_dirs = m.views && !m.has_bend;     // the row's viewdirs, not finite differences
+    if (m.generic) {
+        const ImageDev& gx = m.img[own ? IMG_GX_FINE : IMG_GX_COARSE];
+        p.net = NetFamily::Gen; p.image = own ? IMG_GEN_FINE : IMG_GEN_COARSE; p.name = "gen_kernel";
+        if (gx.stream && !flag(NRNERF_RENDER_NO_X16) && !rows_give_dirs) {
+            p.net = NetFamily::Gx16; p.image = own ? IMG_GX_FINE : IMG_GX_COARSE; p.dispatch = gx.gx.wc; p.name = "gx16_kernel";
+        }
+        return q;
+    }
+    if (m.has_bend) {
+        // (a handle without a fine network keeps its only 16x16x32 trunk image in the fine slot, pack_images)
+        const ImageSlot x16_image = (which || m.fine_is_coarse) ? IMG_FINE_TRUNK_X16 : IMG_COARSE_TRUNK_X16;
+        const bool x16 = !flag(NRNERF_RENDER_NO_X16) && m.img[x16_image].stream;
+        p.net = x16 ? NetFamily::NetX16 : NetFamily::NetTrunk; p.dispatch = trunk_arch(m.arch_id); p.trunk_counter = x16 && dynamic;
+        p.image = x16 ? x16_image : (which ? IMG_FINE_TRUNK : IMG_COARSE_TRUNK);
+        p.name = x16 ? "net_kernel_x16" : "net_kernel (trunk only)";
+        return q;
+    }
+    p.net = NetFamily::NetTrunk; p.image = own ? IMG_FINE : IMG_COARSE; p.dispatch = m.arch_id; p.name = "net_kernel";
+    if (rows_give_dirs) {
+        q.per_point = true; q.point_latents = m.needs_latents != 0;
+        p.S = 1; p.name = "net_kernel (a record per point)";
+    }
+    return q;
+}
+}  // namespace
+extern "C" {
+
+size_t nrnerf_query_workspace_bytes(const nrnerf_model* m, int32_t which, int32_t n_rows, int32_t n_samples) {
+    if (!m || (which != 0 && which != 1) || n_rows <= 0 || n_samples <= 0 || n_samples > NRNERF_MAX_SAMPLES) return 0;
+    const QueryPlan q = plan_query(*m, which, n_rows, n_samples, 0);
+    return q.status == NRNERF_OK ? QueryLayout(*m, q, n_rows, n_samples).total : 0;
+}
+
+int nrnerf_query(const nrnerf_model* m, const nrnerf_query_args* a, void* hip_stream) try {
+    if (!m || !a || a->struct_size != sizeof(nrnerf_query_args)) return NRNERF_ERR_INVALID;
+    if (a->which != 0 && a->which != 1) return NRNERF_ERR_INVALID;
+    if (a->n_rows < 0 || a->n_samples < 1 || a->n_samples > NRNERF_MAX_SAMPLES || a->point_stride < 3 || a->latent_stride < 0) return NRNERF_ERR_INVALID;
+    if (a->flags & ~QUERY_FLAGS) return NRNERF_ERR_INVALID;
+    const nrnerf_sample_outputs& d = a->details;
+    if (d.visibility_weights || d.opacity_alpha) return NRNERF_ERR_INVALID;          // compositing's tensors: nothing is composited here
+    if (a->n_rows == 0) return NRNERF_OK;
+    if (!a->points || !a->raw) return NRNERF_ERR_INVALID;
+    if (m->needs_latents && !a->latents) return NRNERF_ERR_INVALID;
+    if (!m->has_bend && (d.unmasked_offsets || d.masked_offsets || d.rigidity_mask)) return NRNERF_ERR_INVALID;
+    if (m->views && !m->has_bend && !a->viewdirs) return NRNERF_ERR_INVALID;
+    if (m->views && m->has_bend && !m->exact && a->n_samples == 1) return NRNERF_ERR_INVALID;      // no neighbour to difference against (rnh:339-351)
+    const int N = a->n_rows, S = a->n_samples;
+    const QueryPlan q = plan_query(*m, a->which, N, S, a->flags);
+    if (q.status != NRNERF_OK) return q.status;
+    const PassPlan& p = q.pass;
+    const ImageDev& im = m->img[p.image];
+    if (!im.stream) return NRNERF_ERR_UNSUPPORTED;
+    if (a->raw_ch != im.output_ch) return NRNERF_ERR_INVALID;
+    const QueryLayout lay(*m, q, N, S);
+    if (!a->workspace || a->workspace_bytes < lay.total || ((uintptr_t)a->workspace & 255)) return NRNERF_ERR_WORKSPACE;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    DeviceGuard guard(m->device);
+    if (!guard.ok) return NRNERF_ERR_HIP;
+    char* const ws = (char*)a->workspace;
+    float* const raw4 = (float*)(ws + lay.raw4);
+    float* const pts4 = (float*)(ws + lay.pts4);
+    float* const records = (float*)(ws + lay.records);
+    const long long M = (long long)N * S;
+
+    // ---- the inputs in the kernels' layouts: a ray record per row (zeros + the unit direction), and -- no bender -- the points as rows of four
+    QueryPackArgs pk{};
+    pk.points = a->points; pk.stride = a->point_stride; pk.viewdirs = a->viewdirs; pk.n_rows = N; pk.S = S;
+    pk.init_pts = d.initial_input_pts; pk.records = records;
+    if (!m->has_bend) { pk.pts4 = pts4; pk.in_pts = d.input_pts; }
+    if (q.per_point) {
+        pk.point_records = (float*)(ws + lay.point_records);
+        if (q.point_latents) { pk.latents_out = (float*)(ws + lay.point_latents); pk.latents = a->latents; pk.lat_stride = a->latent_stride; pk.lat = m->latent_size; }
+    }
+    if (launch_query_pack(pk, stream) != hipSuccess) return NRNERF_ERR_HIP;
+
+    // the call as a render call of one pass: RenderCall's network step, profile records and work counters
+    nrnerf_render_args r{};
+    r.struct_size = sizeof(r);
+    r.n_rays = N; r.n_samples = S; r.rays = records; r.ray_stride = 11; r.latents = a->latents; r.latent_stride = a->latent_stride;
+    r.has_rigidity_cutoff = a->has_rigidity_cutoff; r.rigidity_cutoff = a->rigidity_cutoff;
+    r.has_test_time_scaling = a->has_test_time_scaling; r.test_time_scaling = a->test_time_scaling;
+    r.has_removal_threshold = m->has_bend ? a->has_removal_threshold : 0; r.removal_threshold = a->removal_threshold;
+    r.detailed_output = a->detailed_output; r.raw = a->raw; r.flags = a->flags;
+    if (q.per_point) {
+        r.n_rays = (int32_t)M; r.n_samples = 1; r.rays = pk.point_records;
+        if (q.point_latents) { r.latents = pk.latents_out; r.latent_stride = m->latent_size; }
+    }
+    RenderPlan rp;
+    rp.generic = m->generic != 0; rp.bend_x16 = q.bend_x16;
+    RenderCall call(m, &r, rp, stream, raw4, pts4, (unsigned*)(ws + lay.counters));
+    if (p.bend_dynamic) (void)call.counter(true, 0);           // (the memset node ahead of every timed launch)
+    if (!q.per_point && !m->has_bend) call.given_pts = pts4;
+
+    if (p.bend == BendStep::Compiled) {
+        const ImageDev& bi = q.bend_x16 ? m->bend_x16 : m->bend_only;
+        BendPointArgs b{};
+        b.b.latents = a->latents; b.b.lat_stride = a->latent_stride; b.b.n_rays = N; b.b.n_per_ray = S; b.b.out_stride = S;
+        b.b.wstream = bi.stream; b.b.bias = bi.bias; b.b.bent4 = pts4; b.b.knobs = call.kn;
+        b.b.work_counter = call.counter(p.bend_dynamic, (size_t)16 * BEND_COUNTERS_PER_LAUNCH * p.which);
+        b.src.points = a->points; b.src.stride = a->point_stride; b.src.unmasked = d.unmasked_offsets; b.src.masked = d.masked_offsets;
+        const hipError_t e = call.timed(call.work(p.bend_slot, q.bend_x16 ? "bend_kernel_x16 (point source)" : "bend_kernel (point source)", bi, S), [&] {
+            return q.bend_x16 ? launch_bend_points_x16(bender_arch_of(m), b, m->num_cus, stream)
+                              : launch_bend_points(m->precision, bender_arch_of(m), b, m->num_cus, stream);
+        });
+        if (e != hipSuccess) return NRNERF_ERR_HIP;
+    }
+    if (call.network_step(p, CompositeArgs{}) != hipSuccess) return NRNERF_ERR_HIP;
+    if (m->has_bend) {
+        // input_pts / rigidity_mask are bent4's columns; the removal knob (only under detailed_output, rnh:308-311) on the caller's raw rows
+        QueryUnpackArgs u{};
+        u.bent4 = pts4; u.n = M; u.in_pts = d.input_pts; u.rigidity = d.rigidity_mask;
+        u.raw = a->raw; u.raw_ch = a->raw_ch; u.has_removal = a->detailed_output && a->has_removal_threshold; u.removal = a->removal_threshold;
+        if ((u.in_pts || u.rigidity || u.has_removal) && launch_query_unpack(u, stream) != hipSuccess) return NRNERF_ERR_HIP;
+    }
+    return NRNERF_OK;
+} NRN_CATCH
+
+int nrnerf_grid_points(const float min_point[3], const float max_point[3], int32_t gx, int32_t gy, int32_t gz, int64_t first_row,
+                       int32_t n_rows, float* pts4, void* hip_stream) try {
+    if (!min_point || !max_point || gx < 1 || gy < 1 || gz < 1 || first_row < 0 || n_rows < 0) return NRNERF_ERR_INVALID;
+    if (first_row + n_rows > (int64_t)gy * gz) return NRNERF_ERR_INVALID;
+    if (n_rows == 0) return NRNERF_OK;
+    if (!pts4) return NRNERF_ERR_INVALID;
+    GridArgs g{};
+    for (int c = 0; c < 3; ++c) { g.lo[c] = min_point[c]; g.hi[c] = max_point[c]; }
+    g.g[0] = gx; g.g[1] = gy; g.g[2] = gz; g.first_row = first_row; g.n_rows = n_rows; g.pts4 = pts4;
+    return on_owner_of(pts4, [&] { return status_of(launch_grid_points(g, (hipStream_t)hip_stream)); });
+} NRN_CATCH
+
+int nrnerf_field_from_raw(const float* raw, int32_t raw_ch, int64_t n, float* sigma, uint8_t* rgb8, void* hip_stream) try {
+    if (n < 0 || raw_ch < 4) return NRNERF_ERR_INVALID;
+    if (n == 0 || (!sigma && !rgb8)) return NRNERF_OK;
+    if (!raw) return NRNERF_ERR_INVALID;
+    return on_owner_of(raw, [&] { return status_of(launch_field_from_raw(raw, raw_ch, n, sigma, rgb8, (hipStream_t)hip_stream)); });
 } NRN_CATCH
 
 int nrnerf_generate_rays(const nrnerf_camera* cam, float near_plane, float far_plane, float* rays_out,

@@ -14,6 +14,7 @@
 // nrnerf_net_impl.h -- so a bent point computed here equals the fused kernel's bit for bit.
 #pragma once
 #include "nrnerf_net_impl.h"
+#include "nrnerf_bend_points.h"
 
 namespace nrn {
 
@@ -74,8 +75,13 @@ struct WResident {
     }
 };
 
-template <class P, class A, int WAVES>
-__global__ void __launch_bounds__(WAVES * 64, (P::KH == 1) ? 4 : 2) bend_kernel(const BendArgs a) {
+// POINTS (the point-source variant, nrnerf_bend_points.h; the kernel's argument record is then BendPointArgs): the samples are READ -- sample k of
+// row r = points[(r * n_per_ray + k) * stride ..] (nrnerf_query: the reference's network_query_fn, train.py:57-105) -- instead of placed on a ray
+// (rays / z / rank are not read; out_stride = n_per_ray), and the offsets of rnh:541-573 can be stored next to bent4.  Every difference is an
+// `if constexpr`: the ray-source instantiation compiles to what it was.
+template <class P, class A, int WAVES, bool POINTS = false>
+__global__ void __launch_bounds__(WAVES * 64, (P::KH == 1) ? 4 : 2) bend_kernel(const std::conditional_t<POINTS, BendPointArgs, BendArgs> args) {
+    const BendArgs& a = bend_args_of(args);
     static_assert(P::KH == 1 ? WAVES == 4 : WAVES == 8, "fp32 mode: workgroups of four waves, four of them per CU; 16-bit modes: eight waves");
     using PL = Plan<P, A, true, false, false>;                  // bender + rigidity layers only
     using PE = std::conditional_t<P::KH == 1, PolF32, PolF16>;  // as in the fused kernels (nrnerf_plan.h frag_is_f16)
@@ -120,6 +126,25 @@ __global__ void __launch_bounds__(WAVES * 64, (P::KH == 1) ? 4 : 2) bend_kernel(
         in.ok = k < n;
         const int kc = in.ok ? k : n - 1;
         in.ray = ray;
+        if constexpr (POINTS) {
+            // the point itself (clamped index: a lane beyond the row's end re-reads the row's last point and writes nothing)
+            const BendPointSrc& ps = bend_points_of(args);
+            const bool pt_vec = ps.stride == 4 && (((size_t)ps.points & 15) == 0);
+            const float* pp = ps.points + ((size_t)ray * n + kc) * ps.stride;
+            if (pt_vec) {
+                const f32x4 q = *(const f32x4*)pp;
+                in.o[0] = q[0]; in.o[1] = q[1]; in.o[2] = q[2];
+            } else {
+                in.o[0] = pp[0]; in.o[1] = pp[1]; in.o[2] = pp[2];
+            }
+            cfloat_p lpp = (cfloat_p)(a.latents + (size_t)ray * a.lat_stride);
+#pragma unroll
+            for (int c = 0; c < A::LAT; ++c) in.lat[c] = lpp[c];
+            in.d[0] = in.d[1] = in.d[2] = 0.0f;
+            in.z = 0.0f;
+            in.row = kc;
+            return;
+        }
         cfloat_p rp = (cfloat_p)(a.rays + (size_t)ray * a.ray_stride);
         cfloat_p lp = (cfloat_p)(a.latents + (size_t)ray * a.lat_stride);
 #pragma unroll
@@ -147,6 +172,7 @@ __global__ void __launch_bounds__(WAVES * 64, (P::KH == 1) ? 4 : 2) bend_kernel(
         const int out_ray = cur.ray, out_row = cur.row;
         float p[3] = {__fadd_rn(cur.o[0], __fmul_rn(cur.d[0], cur.z)), __fadd_rn(cur.o[1], __fmul_rn(cur.d[1], cur.z)),
                       __fadd_rn(cur.o[2], __fmul_rn(cur.d[2], cur.z))};                  // train.py:921-923
+        if constexpr (POINTS) { p[0] = cur.o[0]; p[1] = cur.o[1]; p[2] = cur.o[2]; }      // (the point as given: no o + d z rounding of it)
         const float* lat = cur.lat;
         auto binval = [&](auto idxc) -> float {
             constexpr int idx = decltype(idxc)::value;
@@ -227,6 +253,21 @@ __global__ void __launch_bounds__(WAVES * 64, (P::KH == 1) ? 4 : 2) bend_kernel(
 
         float rig_mask = (tanhf(logit) + 1.0f) / 2.0f;                                       // rnh:559-561
         if (a.knobs.has_cutoff && rig_mask <= a.knobs.cutoff) rig_mask = 0.0f;               // rnh:563-564
+        if constexpr (POINTS) {                 // the detail tensors of rnh:541-573, when asked for (rigidity is bent4.w)
+            const BendPointSrc& ps = bend_points_of(args);
+            if (ok && h == 0) {
+                const size_t so = ((size_t)out_ray * a.out_stride + out_row) * 3;
+                if (ps.unmasked) { ps.unmasked[so] = off[0]; ps.unmasked[so + 1] = off[1]; ps.unmasked[so + 2] = off[2]; }
+                if (ps.masked) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        float mo = __fmul_rn(rig_mask, off[c]);                              // rnh:567
+                        if (a.knobs.has_scaling) mo = __fmul_rn(mo, a.knobs.scaling);        // rnh:568-569
+                        ps.masked[so + c] = mo;
+                    }
+                }
+            }
+        }
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             float mo = __fmul_rn(rig_mask, off[c]);                                          // rnh:567
@@ -238,11 +279,13 @@ __global__ void __launch_bounds__(WAVES * 64, (P::KH == 1) ? 4 : 2) bend_kernel(
     }
 }
 
-template <class P, class A, int WAVES>
-static hipError_t launch_bend_one(const BendArgs& a, int num_cus, hipStream_t stream) {
+// ARGS = BendArgs: the ray-source kernel; BendPointArgs: the point-source one
+template <class P, class A, int WAVES, class ARGS>
+static hipError_t launch_bend_one(const ARGS& args, int num_cus, hipStream_t stream) {
     using PL = Plan<P, A, true, false, false>;
     const size_t lds = (size_t)PL::NFRAGS * P::FRAG_BYTES + (size_t)PL::NTILES * 32 * sizeof(float);
-    auto kern = bend_kernel<P, A, WAVES>;
+    const BendArgs& a = bend_args_of(args);
+    auto kern = bend_kernel<P, A, WAVES, std::is_same_v<ARGS, BendPointArgs>>;
     static bool attr_set[64] = {};       // function attributes are per device (idempotent; racing threads set the same value)
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
@@ -261,7 +304,7 @@ static hipError_t launch_bend_one(const BendArgs& a, int num_cus, hipStream_t st
     const long long per_cu = (P::KH == 1) ? 4 : ((!P::SPLIT) ? 2 : 1);
     const long long resident = per_cu * num_cus;
     const int grid = (int)(want < resident ? want : resident);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, args);
     return hipGetLastError();
 }
 

@@ -34,8 +34,13 @@ namespace nrn {
 #endif
 
 // PERRAY: a latent code per ray (lat_stride != 0); false: one code for the whole launch (a frame render), read once per wave
-template <class A, int WAVES, int NB, bool PERRAY>
-__global__ void __launch_bounds__(WAVES * 64, NRN_BX16_OCC) bend_kernel_x16(const BendArgs a) {
+// POINTS (the point-source variant, nrnerf_bend_points.h; the kernel's argument record is then BendPointArgs): the samples are READ -- sample k of
+// row r = points[(r * n_per_ray + k) * stride ..] (nrnerf_query: the reference's network_query_fn, train.py:57-105) -- instead of placed on a ray
+// (rays / z / rank are not read; out_stride = n_per_ray), and the offsets of rnh:541-573 can be stored next to bent4.  Every difference is an
+// `if constexpr`: the ray-source instantiations compile to what they were.
+template <class A, int WAVES, int NB, bool PERRAY, bool POINTS = false>
+__global__ void __launch_bounds__(WAVES * 64, NRN_BX16_OCC) bend_kernel_x16(const std::conditional_t<POINTS, BendPointArgs, BendArgs> args) {
+    const BendArgs& a = bend_args_of(args);
     using P = PolF16;
     using PL = PlanX16Bend<A>;
     using frag = typename P::frag;
@@ -84,18 +89,34 @@ __global__ void __launch_bounds__(WAVES * 64, NRN_BX16_OCC) bend_kernel_x16(cons
             const bool ok = blk_ok && k < npr;
             const int kc = k < npr ? k : npr - 1;
             in[b].kc = kc;
-            const float* rp = a.rays + (size_t)ray * a.ray_stride;
-            if (ray_vec) {
-                const f32x4 r0 = *(const f32x4*)rp, r1 = *(const f32x4*)(rp + 4);
-                in[b].o[0] = r0[0]; in[b].o[1] = r0[1]; in[b].o[2] = r0[2]; in[b].d[0] = r0[3]; in[b].d[1] = r1[0]; in[b].d[2] = r1[1];
-                in[b].near = r1[2]; in[b].far = r1[3];
+            if constexpr (POINTS) {
+                // the point itself (clamped index: a lane beyond the row's end re-reads the row's last point and writes nothing); the 16-byte
+                // load is chosen per launch (wave-uniform), as ray_vec / lat_vec
+                const BendPointSrc& ps = bend_points_of(args);
+                const bool pt_vec = ps.stride == 4 && (((size_t)ps.points & 15) == 0);
+                const float* pp = ps.points + ((size_t)ray * npr + kc) * ps.stride;
+                if (pt_vec) {
+                    const f32x4 q = *(const f32x4*)pp;
+                    in[b].o[0] = q[0]; in[b].o[1] = q[1]; in[b].o[2] = q[2];
+                } else {
+                    in[b].o[0] = pp[0]; in[b].o[1] = pp[1]; in[b].o[2] = pp[2];
+                }
+                in[b].d[0] = in[b].d[1] = in[b].d[2] = 0.0f; in[b].near = in[b].far = in[b].z = 0.0f;
+                in[b].idx = ok ? ray * a.out_stride + kc : -1;
             } else {
-                in[b].o[0] = rp[0]; in[b].o[1] = rp[1]; in[b].o[2] = rp[2]; in[b].d[0] = rp[3]; in[b].d[1] = rp[4]; in[b].d[2] = rp[5];
-                in[b].near = rp[6]; in[b].far = rp[7];
+                const float* rp = a.rays + (size_t)ray * a.ray_stride;
+                if (ray_vec) {
+                    const f32x4 r0 = *(const f32x4*)rp, r1 = *(const f32x4*)(rp + 4);
+                    in[b].o[0] = r0[0]; in[b].o[1] = r0[1]; in[b].o[2] = r0[2]; in[b].d[0] = r0[3]; in[b].d[1] = r1[0]; in[b].d[2] = r1[1];
+                    in[b].near = r1[2]; in[b].far = r1[3];
+                } else {
+                    in[b].o[0] = rp[0]; in[b].o[1] = rp[1]; in[b].o[2] = rp[2]; in[b].d[0] = rp[3]; in[b].d[1] = rp[4]; in[b].d[2] = rp[5];
+                    in[b].near = rp[6]; in[b].far = rp[7];
+                }
+                in[b].z = a.z ? a.z[(size_t)ray * npr + kc] : 0.0f;
+                const int row = a.rank ? (int)a.rank[(size_t)ray * npr + kc] : kc;
+                in[b].idx = ok ? ray * a.out_stride + row : -1;           // (n_rays * out_stride < 2^31: the launcher checks)
             }
-            in[b].z = a.z ? a.z[(size_t)ray * npr + kc] : 0.0f;
-            const int row = a.rank ? (int)a.rank[(size_t)ray * npr + kc] : kc;
-            in[b].idx = ok ? ray * a.out_stride + row : -1;           // (n_rays * out_stride < 2^31: the launcher checks)
             if constexpr (PERRAY) {
                 const float* lp = a.latents + (size_t)ray * a.lat_stride + 8 * g;
                 if (lat_vec) {
@@ -157,7 +178,7 @@ __global__ void __launch_bounds__(WAVES * 64, NRN_BX16_OCC) bend_kernel_x16(cons
         static_for<0, NB>([&](auto bc) {
             constexpr int b = decltype(bc)::value;
             float z = cur[b].z;
-            if (!a.z) {                                // coarse depths (train.py:847-852), as in the fused kernels
+            if (!POINTS && !a.z) {                             // coarse depths (train.py:847-852), as in the fused kernels
                 const float t = lin01(cur[b].kc, npr), near = cur[b].near, far = cur[b].far;
                 if (a.lindisp)
                     z = __fdiv_rn(1.0f, __fadd_rn(__fmul_rn(__fdiv_rn(1.0f, near), __fsub_rn(1.0f, t)), __fmul_rn(__fdiv_rn(1.0f, far), t)));
@@ -167,6 +188,7 @@ __global__ void __launch_bounds__(WAVES * 64, NRN_BX16_OCC) bend_kernel_x16(cons
             out_idx[b] = cur[b].idx;
 #pragma unroll
             for (int c = 0; c < 3; ++c) p[b][c] = __fadd_rn(cur[b].o[c], __fmul_rn(cur[b].d[c], z));       // train.py:921-923
+            if constexpr (POINTS) { p[b][0] = cur[b].o[0]; p[b][1] = cur[b].o[1]; p[b][2] = cur[b].o[2]; }      // (the point as given)
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 bin[b][0][e] = (_Float16)((g == 0 && e < 3) ? p[b][e < 3 ? e : 0] : 0.0f);
@@ -241,6 +263,21 @@ __global__ void __launch_bounds__(WAVES * 64, NRN_BX16_OCC) bend_kernel_x16(cons
                 q[c] = __fadd_rn(p[b][c], mo);                                                   // rnh:570
             }
             if (out_idx[b] >= 0 && g == 0) *(f32x4*)(a.bent4 + (size_t)out_idx[b] * 4) = f32x4{q[0], q[1], q[2], rig_mask};
+            if constexpr (POINTS) {             // the detail tensors of rnh:541-573, when asked for (rigidity is bent4.w)
+                const BendPointSrc& ps = bend_points_of(args);
+                if (out_idx[b] >= 0 && g == 0) {
+                    const size_t so = (size_t)out_idx[b] * 3;
+                    if (ps.unmasked) { ps.unmasked[so] = off[b][0]; ps.unmasked[so + 1] = off[b][1]; ps.unmasked[so + 2] = off[b][2]; }
+                    if (ps.masked) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) {
+                            float mo = __fmul_rn(rig_mask, off[b][c]);                           // rnh:567
+                            if (a.knobs.has_scaling) mo = __fmul_rn(mo, a.knobs.scaling);        // rnh:568-569
+                            ps.masked[so + c] = mo;
+                        }
+                    }
+                }
+            }
         });
         grp = nxt; grp_end = nxt_end;
         if (new_chunk) chunk_at(__builtin_amdgcn_readfirstlane(grabbed), nxt, nxt_end);
@@ -269,13 +306,16 @@ __global__ void __launch_bounds__(WAVES * 64, NRN_BX16_OCC) bend_kernel_x16(cons
 #endif
 }
 
-template <class A>
-static hipError_t launch_bend_x16_t(const BendArgs& a, int num_cus, hipStream_t stream) {
+// ARGS = BendArgs: the ray-source kernel; BendPointArgs: the point-source one
+template <class A, class ARGS>
+static hipError_t launch_bend_x16_t(const ARGS& args, int num_cus, hipStream_t stream) {
+    constexpr bool POINTS = std::is_same_v<ARGS, BendPointArgs>;
+    const BendArgs& a = bend_args_of(args);
     constexpr int WAVES = NRN_BX16_WAVES, NB = NRN_BX16_NB;
     using PL = PlanX16Bend<A>;
     const size_t lds = (size_t)PL::NFRAGS * PolF16::FRAG_BYTES + (size_t)PL::NTILES * 16 * sizeof(float);
     const bool per_ray = a.lat_stride != 0;
-    auto kern = per_ray ? bend_kernel_x16<A, WAVES, NB, true> : bend_kernel_x16<A, WAVES, NB, false>;
+    auto kern = per_ray ? bend_kernel_x16<A, WAVES, NB, true, POINTS> : bend_kernel_x16<A, WAVES, NB, false, POINTS>;
     static bool attr_set[64][2] = {};
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
@@ -290,7 +330,7 @@ static hipError_t launch_bend_x16_t(const BendArgs& a, int num_cus, hipStream_t 
     if (want <= 0) return hipSuccess;
     const long long resident = (long long)NRN_BX16_OCC * num_cus;
     const int grid = (int)(want < resident ? want : resident);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, args);
     return hipGetLastError();
 }
 

@@ -9,6 +9,13 @@ hipError_t launch_bend_x16(int arch, const BendArgs& a, int num_cus, hipStream_t
     if (arch == 1) return launch_bend_x16_t<ArchDeepBend>(a, num_cus, stream);
     return hipErrorInvalidValue;
 }
+// the point-source variant (nrnerf_bend_points.h)
+hipError_t launch_bend_points_x16(int arch, const BendPointArgs& a, int num_cus, hipStream_t stream) {
+    if (a.b.out_stride != a.b.n_per_ray || !a.src.points || a.src.stride < 3) return hipErrorInvalidValue;
+    if (arch == 0) return launch_bend_x16_t<ArchDefault>(a, num_cus, stream);
+    if (arch == 1) return launch_bend_x16_t<ArchDeepBend>(a, num_cus, stream);
+    return hipErrorInvalidValue;
+}
 }  // namespace nrn
 
 #ifdef NRN_TIMING

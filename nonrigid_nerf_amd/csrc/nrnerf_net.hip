@@ -1,6 +1,7 @@
 // nrnerf_net.hip -- host-side dispatch over the compiled network-kernel variants
 // (architecture x precision x bender x view-dependent head; see the VARIANTS list in the Makefile).
 #include "nrnerf_kernels.h"
+#include "nrnerf_bend_points.h"
 
 namespace nrn {
 typedef hipError_t (*launch_fn)(const NetArgs&, int, hipStream_t);
@@ -45,6 +46,21 @@ static const bend_fn BEND_TABLE[2][3] = {
 hipError_t launch_bend(int precision, int arch_id, const BendArgs& a, int num_cus, hipStream_t stream) {
     if (arch_id < 0 || arch_id > 1 || precision < 0 || precision > 2) return hipErrorInvalidValue;
     return BEND_TABLE[arch_id][precision](a, num_cus, stream);
+}
+
+// ... and their point-source variants (nrnerf_bend_points.h), the same set
+typedef hipError_t (*bend_points_fn)(const BendPointArgs&, int, hipStream_t);
+#define NRN_BDECL(n) hipError_t launch_bend_##n##_points(const BendPointArgs&, int, hipStream_t);
+NRN_BDECL(a0_f32) NRN_BDECL(a0_bf16) NRN_BDECL(a0_f16) NRN_BDECL(a1_f32) NRN_BDECL(a1_bf16) NRN_BDECL(a1_f16)
+#undef NRN_BDECL
+static const bend_points_fn BEND_POINTS_TABLE[2][3] = {
+    {launch_bend_a0_f32_points, launch_bend_a0_bf16_points, launch_bend_a0_f16_points},
+    {launch_bend_a1_f32_points, launch_bend_a1_bf16_points, launch_bend_a1_f16_points},
+};
+hipError_t launch_bend_points(int precision, int arch_id, const BendPointArgs& a, int num_cus, hipStream_t stream) {
+    if (arch_id < 0 || arch_id > 1 || precision < 0 || precision > 2) return hipErrorInvalidValue;
+    if (a.b.out_stride != a.b.n_per_ray || !a.src.points || a.src.stride < 3) return hipErrorInvalidValue;
+    return BEND_POINTS_TABLE[arch_id][precision](a, num_cus, stream);
 }
 
 hipError_t launch_net(int precision, bool has_bend, bool views, int arch_id, const NetArgs& a, int num_cus, hipStream_t stream) {

@@ -9,7 +9,8 @@ Call contract mirrored:
   for every caller (``render_path``, ``determine_nerf_volume_extent``, free_viewpoint_rendering.py).
 * weights are read from the ``network_fn`` / ``network_fine`` modules (``pts_linears``,
   ``output_linear``) and from ``network_fn.ray_bender[0]`` (``network``, ``rigidity_network``);
-  ``network_query_fn`` is ignored (the encoding / chunking it closes over is fused in the kernel).
+  ``network_query_fn`` is ignored by ``render_rays`` (the encoding / chunking it closes over is fused in the kernel); the function
+  itself -- the networks on arbitrary points -- is ``network_query_fn`` / ``query_points`` below (``nrnerf_query``).
 * the editing knobs free_viewpoint_rendering.py:264-283 mutates on the modules are read per call.
 * output: dict with exactly the reference's keys / shapes / dtypes (train.py:952-972), freshly
   allocated on the rays' device.
@@ -506,6 +507,81 @@ class Model:
             self.note_use(dev)
         return out
 
+    def query(self, points: torch.Tensor, latents: torch.Tensor | None = None, viewdirs: torch.Tensor | None = None, which: int = 0,
+              detailed_output: bool = False, rigidity_cutoff=None, test_time_scaling=None, removal_threshold=None,
+              flags: int | None = None, out: dict | None = None):
+        """``nrnerf_query``: the network (``which`` 0 = coarse, 1 = fine), ray bender included, on ``points [N, S, 3 | 4]`` -- the reference's
+        ``run_network`` (train.py:57-105).  ``latents [N, latent_size]`` (or one row, stride 0) and ``viewdirs [N, 3]`` are per row.  Returns
+        ``raw [N, S, C]``, or ``(raw, details)`` under ``detailed_output`` (the keys of rnh:297-306).  ``out``: preallocated tensors by key
+        (``raw``, ``rigidity_mask``, ...) to write into instead of new ones -- the grid sampler's slabs."""
+        if points.dim() != 3 or points.shape[-1] not in (3, 4):
+            raise ValueError(f"points must have shape (N, S, 3) or (N, S, 4), got {tuple(points.shape)}")
+        N, S = int(points.shape[0]), int(points.shape[1])
+        if not 1 <= S <= _lib.MAX_SAMPLES:
+            raise ValueError(f"1 <= samples per row <= {_lib.MAX_SAMPLES}, got {S}")
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        points = points.to(**f32).contiguous()
+        a = _lib.QueryArgs()
+        a.struct_size = C.sizeof(_lib.QueryArgs)
+        a.which, a.n_rows, a.n_samples = int(which), N, S
+        a.points, a.point_stride = points.data_ptr(), int(points.shape[-1])
+        if self.needs_latents:
+            if latents is None:
+                raise ValueError("ray_bending_latents are required (ray bender or time-conditioned baseline)")
+            if latents.dim() != 2 or latents.shape[0] != N or latents.shape[1] != self.latent_size:
+                raise ValueError(f"ray_bending_latents must have shape ({N}, {self.latent_size}), got {tuple(latents.shape)}")
+            if latents.stride(0) == 0 and latents.stride(1) == 1 and latents.dtype == torch.float32 and latents.device == dev:
+                a.latents, a.latent_stride = latents.data_ptr(), 0           # one code for the call
+            else:
+                latents = latents.to(**f32).contiguous()
+                a.latents, a.latent_stride = latents.data_ptr(), latents.shape[1]
+        if viewdirs is not None:
+            if viewdirs.dim() != 2 or tuple(viewdirs.shape) != (N, 3):
+                raise ValueError(f"viewdirs must have shape ({N}, 3), got {tuple(viewdirs.shape)}")
+            viewdirs = viewdirs.to(**f32).contiguous()
+            a.viewdirs = viewdirs.data_ptr()
+        got = {}
+
+        def new(key, *shape):
+            t = (out or {}).get(key)
+            if t is None:
+                t = torch.empty(*shape, **f32)
+            elif tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+                raise ValueError(f"out[{key!r}] must be a contiguous float32 tensor of shape {shape} on {dev}")
+            got[key] = t
+            return t.data_ptr()
+
+        ch = self.output_ch if which else self.coarse_output_ch
+        a.raw, a.raw_ch = new("raw", N, S, ch), ch
+        if detailed_output:
+            a.details.initial_input_pts = new("initial_input_pts", N, S, 3)
+            a.details.input_pts = new("input_pts", N, S, 3)
+            if self.has_bender:
+                a.details.unmasked_offsets = new("unmasked_offsets", N, S, 3)
+                a.details.masked_offsets = new("masked_offsets", N, S, 3)
+                a.details.rigidity_mask = new("rigidity_mask", N, S, 1)
+        elif out and "rigidity_mask" in out and self.has_bender:
+            a.details.rigidity_mask = new("rigidity_mask", N, S, 1)
+        a.detailed_output = int(detailed_output)
+        a.flags = (_lib.render_flags_from_env() if flags is None else int(flags)) & _lib.QUERY_FLAGS
+        if rigidity_cutoff is not None:
+            a.has_rigidity_cutoff, a.rigidity_cutoff = 1, float(rigidity_cutoff)
+        if test_time_scaling is not None:
+            a.has_test_time_scaling, a.test_time_scaling = 1, float(test_time_scaling)
+        if removal_threshold is not None:
+            a.has_removal_threshold, a.removal_threshold = 1, float(removal_threshold)
+        if N > 0:
+            nbytes = self.lib.nrnerf_query_workspace_bytes(self.handle, int(which), N, S)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                ws = self._workspace(nbytes + 256, stream)
+                a.workspace, a.workspace_bytes = (ws.data_ptr() + 255) // 256 * 256, nbytes
+                _lib.check(self.lib.nrnerf_query(self.handle, C.byref(a), C.c_void_p(stream)), "nrnerf_query")
+                self.note_use(dev)
+        raw = got.pop("raw")
+        return (raw, got) if detailed_output else raw
+
     def note_use(self, dev=None):
         """Kernels reading this handle's weights were just queued on the current stream: remember an event there, so that
         a later weight refresh issued from ANOTHER stream can order itself after them (update_from_device).  The
@@ -780,6 +856,102 @@ def render_rays(ray_batch, network_fn, network_query_fn=None, N_samples=64, retr
             if torch.isnan(v).any() or torch.isinf(v).any():
                 print(f"! [Numerical Error] {k} contains nan or inf.")
     return ret
+
+
+# --------------------------------------------------------------------------------------------
+# the field itself: the networks on arbitrary points (the reference's network_query_fn, train.py:57-105, 633-649)
+# --------------------------------------------------------------------------------------------
+QUERY_ROW = 64           # samples per row a FLAT point array is laid out in
+
+
+def plan_flat_rows(n_points: int, row: int = QUERY_ROW):
+    """How a flat ``[M, 3]`` point array becomes rows: ``(n_rows, row, n_pad)`` -- rows of ``row`` points, the last one padded with
+    ``n_pad`` repeats of the last point (their outputs are dropped).  Pure."""
+    n_points, row = int(n_points), int(row)
+    if n_points < 0 or row < 1:
+        raise ValueError("n_points >= 0 and row >= 1")
+    n_rows = (n_points + row - 1) // row
+    return n_rows, row, n_rows * row - n_points
+
+
+def _query_knobs(network_fn):
+    rb = _bender_of(network_fn)
+    return dict(rigidity_cutoff=getattr(rb, "rigidity_test_time_cutoff", None) if rb is not None else None,
+                test_time_scaling=getattr(rb, "test_time_scaling", None) if rb is not None else None,
+                removal_threshold=getattr(network_fn, "test_time_nonrigid_object_removal_threshold", None))
+
+
+def query_points(points, network_fn, latents=None, viewdirs=None, *, detailed_output=False, precision=None, flags=None):
+    """``network_fn`` (ray bender included) on ``points``: ``[N, S, 3]`` -- N rows of S samples, ``latents [N, latent_size]`` and ``viewdirs
+    [N, 3]`` per row -- or a flat ``[M, 3]`` with ``latents`` / ``viewdirs`` of one row (or ``[M, .]`` rows that are all the same code is NOT
+    assumed: flat input takes ONE code and ONE direction for all points).  Returns ``raw`` (``[N, S, C]`` / ``[M, C]``), or ``(raw, details)``
+    under ``detailed_output``.  Flat input is laid out as rows of 64, the last row padded by repeating its last point; padded outputs are
+    dropped.  With a view-dependent head behind a ray bender the direction of a sample is the finite difference ALONG ITS ROW (rnh:339-351),
+    so flat input is refused there (``ValueError``): the row structure carries meaning.  The knobs (``rigidity_test_time_cutoff``,
+    ``test_time_scaling``, ``test_time_nonrigid_object_removal_threshold``) are read from the modules as ``render_rays`` reads them; the handle
+    comes from ``get_model`` (same cache, same staleness rules).  Raises ``Unsupported`` for what the library has no kernel for."""
+    if points.device.type != "cuda":
+        raise Unsupported("points are not on a ROCm device")
+    if _trains(network_fn, None, points, latents):
+        raise Unsupported("autograd is enabled (a query has no gradient)")
+    has_bender = _bender_of(network_fn) is not None
+    views = bool(getattr(network_fn, "use_viewdirs", False))
+    if views and has_bender and not getattr(network_fn, "approx_nonrigid_viewdirs", True):
+        raise Unsupported("exact (Jacobian) view directions in a point query")
+    flat = points.dim() == 2
+    if flat:
+        if views and has_bender:
+            raise ValueError("flat points with a view-dependent head behind a ray bender: the view direction of a sample is taken along its "
+                             "row (rnh:339-351), pass [N, S, 3]")
+        M = int(points.shape[0])
+        n_rows, row, n_pad = plan_flat_rows(M)
+        if n_pad:
+            points = torch.cat([points, points[-1:].expand(n_pad, -1)], 0)
+        points = points.reshape(n_rows, row, points.shape[-1])
+        if latents is not None:
+            if latents.dim() == 1:
+                latents = latents[None]
+            if latents.shape[0] != 1:
+                raise ValueError("flat points take one latent code [1, latent_size]")
+            latents = latents.to(device=points.device, dtype=torch.float32).contiguous().expand(n_rows, -1)
+        if viewdirs is not None:
+            if viewdirs.dim() == 1:
+                viewdirs = viewdirs[None]
+            if viewdirs.shape[0] != 1:
+                raise ValueError("flat points take one view direction [1, 3]")
+            viewdirs = viewdirs.expand(n_rows, -1)
+    elif points.dim() != 3:
+        raise ValueError(f"points must be [N, S, 3] or [M, 3], got {tuple(points.shape)}")
+    if views and has_bender and points.shape[1] == 1:
+        raise Unsupported("one sample per row with a view-dependent head behind a ray bender (no neighbour to difference against)")
+    if views and not has_bender and viewdirs is None:
+        raise ValueError("a view-dependent head without ray bender needs viewdirs")
+    model = get_model(network_fn, None, precision=precision, device=points.device)
+    try:
+        res = model.query(points, latents, viewdirs, 0, detailed_output=detailed_output, flags=flags, **_query_knobs(network_fn))
+    except _lib.NrnerfError as e:
+        if e.status != _lib.ERR_UNSUPPORTED:
+            raise
+        raise Unsupported(str(e)) from e
+    if not flat:
+        return res
+    cut = lambda t: t.reshape(-1, t.shape[-1])[:M]
+    return (cut(res[0]), {k: cut(v) for k, v in res[1].items()}) if detailed_output else cut(res)
+
+
+def network_query_fn(inputs, viewdirs, additional_pixel_information, network_fn, detailed_output=False):
+    """The reference's ``render_kwargs["network_query_fn"]`` (train.py:633-649 -> run_network, train.py:57-105): signature and return shapes,
+    on ``query_points``.  A call the library cannot take goes to the function ``install()`` saved, if there is one (with a FallbackWarning),
+    and raises ``Unsupported`` otherwise."""
+    latents = None if additional_pixel_information is None else additional_pixel_information.get("ray_bending_latents")
+    try:
+        return query_points(inputs, network_fn, latents, viewdirs, detailed_output=detailed_output)
+    except Unsupported as e:
+        ref = _fallbacks.get("network_query_fn")
+        if ref is None:
+            raise Unsupported(f"no HIP kernel for this query ({e}) and no reference function installed to defer to") from e
+        _note_fallback("network_query_fn", str(e))
+        return ref(inputs, viewdirs, additional_pixel_information, network_fn, detailed_output=detailed_output)
 
 
 def _draw_randoms(ray_batch, N_samples, N_importance, perturb, raw_noise_std):
