@@ -904,6 +904,45 @@ int nrnerf_grid_points(const float min_point[3], const float max_point[3], int32
  * truncating to8b ((255 * clip(x, 0, 1)).astype(uint8)).  Either output may be NULL. */
 int nrnerf_field_from_raw(const float* raw, int32_t raw_ch, int64_t n, float* sigma, uint8_t* rgb8, void* hip_stream);
 
+/* ---- ABI 10 (additions): an iso-surface mesh of a volume on the grid of nrnerf_grid_points.
+ *
+ * Marching tetrahedra over the Kuhn triangulation of each cell (six tetrahedra, sixteen cases each, no ambiguous configuration): the mesh
+ * is closed away from the box faces and every triangle's normal points from inside (value >= level; NaN is outside) to outside.  One mesh
+ * vertex per active grid edge / face diagonal / cell diagonal, shared by every triangle around it, linearly interpolated in double and
+ * rounded to fp32 once; vertices ascending by (owner grid vertex, slot), triangles by (cell, tetrahedron, triangle); zero-area triangles are
+ * kept.  The full definitions -- owner and slot of an edge, the sixteen cases, the optional normals -- are in csrc/nrnerf_isosurface.h and
+ * DESIGN.md section 3.11.  The same bytes on every run.
+ * Two calls around one host read: nrnerf_isosurface_count classifies the grid, scans, and writes totals[2] = {vertices, triangles}; the
+ * caller reads them, allocates, and nrnerf_isosurface_emit writes the mesh FROM THE SAME WORKSPACE (same value, grid and level).  emit stores
+ * nothing at or beyond the capacities n_vertices / n_triangles: with capacities below the totals it writes the prefix of both arrays and
+ * answers NRNERF_OK (a written face may then name a vertex that was not stored).  Device pointers only, asynchronous on the stream,
+ * allocates nothing.  A grid with any g == 1 has no cells: count writes {0, 0}, emit writes nothing, neither touches the workspace.
+ * NRNERF_ERR_INVALID: a NULL record / value / workspace (when bytes are needed) / totals (count) / vertices or faces (emit, with a capacity
+ * > 0), a wrong struct_size, a g < 1, a negative capacity, memory that is not device memory.  NRNERF_ERR_UNSUPPORTED: more than 2^30 grid
+ * vertices; a capacity of 2^31 or more (faces are int32).  NRNERF_ERR_WORKSPACE: fewer than nrnerf_isosurface_workspace_bytes() bytes, or a
+ * base that is not 256-byte aligned. */
+typedef struct nrnerf_isosurface_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_isosurface_args) */
+    const float* value;         /* [gz, gy, gx] float32 (the layout of a density volume sampled row by row with nrnerf_grid_points) */
+    int32_t gx, gy, gz;         /* the grid, each >= 1 */
+    float min_point[3];         /* the box, as in nrnerf_grid_points */
+    float max_point[3];
+    float level;
+    void* workspace;           /* >= nrnerf_isosurface_workspace_bytes(gx, gy, gz), 256-byte aligned */
+    size_t workspace_bytes;
+    int64_t* totals;            /* count: out [2] = {vertices, triangles} */
+    float* vertices;            /* emit: out [n_vertices, 3] */
+    float* normals;             /* emit: out [n_vertices, 3] unit -grad value, or NULL */
+    int32_t* faces;             /* emit: out [n_triangles, 3] vertex indices */
+    int64_t n_vertices;         /* capacities of the outputs, 0 <= n < 2^31 */
+    int64_t n_triangles;
+} nrnerf_isosurface_args;
+/* 0 for a grid without cells (any g <= 1) or beyond 2^30 vertices; else, with n = gx gy gz and nb = ceil(n / 256), the sum of
+ * 4 n, 4 nb, 4 nb, 8 nb, 8 nb and n bytes, each rounded up to a multiple of 256. */
+size_t nrnerf_isosurface_workspace_bytes(int32_t gx, int32_t gy, int32_t gz);
+int nrnerf_isosurface_count(const nrnerf_isosurface_args* args, void* hip_stream);
+int nrnerf_isosurface_emit(const nrnerf_isosurface_args* args, void* hip_stream);
+
 /* Host-only packing (no device needed): writes the MFMA-fragment weight stream + unit table + bias
  * table of one pass exactly as nrnerf_model_create uploads them.  which: 0 = coarse, 1 = fine, 2 = fine without the
  * bender layers, 3 = bender + rigidity layers alone (2, 3: the split-bender path; need a bender and not the exact view directions),

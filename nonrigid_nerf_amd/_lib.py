@@ -327,6 +327,28 @@ class QueryArgs(C.Structure):
 QUERY_FLAGS = RENDER_NO_X16 | RENDER_BENDER_32X32 | RENDER_FIXED_SHARES      # the render flags nrnerf_query honours; any other bit: INVALID
 
 
+class IsosurfaceArgs(C.Structure):
+    """nrnerf_isosurface_args (ABI 10 additions): marching tetrahedra on a volume of the grid, count -> host read of the totals -> emit."""
+    _fields_ = [("struct_size", C.c_uint32), ("value", C.c_void_p), ("gx", C.c_int32), ("gy", C.c_int32), ("gz", C.c_int32),
+                ("min_point", C.c_float * 3), ("max_point", C.c_float * 3), ("level", C.c_float),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("totals", C.c_void_p),
+                ("vertices", C.c_void_p), ("normals", C.c_void_p), ("faces", C.c_void_p),
+                ("n_vertices", C.c_int64), ("n_triangles", C.c_int64)]
+
+
+ISO_BLOCK, ISO_SCAN_CHUNK, ISO_MAX_VERTICES = 256, 4096, 1 << 30      # csrc/nrnerf_isosurface.h
+
+
+def isosurface_workspace_bytes(gx: int, gy: int, gz: int) -> int:
+    """nrnerf_isosurface_workspace_bytes restated: per grid vertex a 4-byte offset word and a corner byte, per block
+    of 256 vertices two 4-byte sums and two 8-byte bases; every array rounded up to 256 bytes.  0: no cells, or beyond 2^30 vertices."""
+    n = gx * gy * gz
+    if min(gx, gy, gz) < 2 or n > ISO_MAX_VERTICES:
+        return 0
+    nb = (n + ISO_BLOCK - 1) // ISO_BLOCK
+    return sum((b + 255) // 256 * 256 for b in (4 * n, 4 * nb, 4 * nb, 8 * nb, 8 * nb, n))
+
+
 EXPORTS = {
     "nrnerf_abi_version": (C.c_int, []),
     "nrnerf_strerror": (C.c_char_p, [C.c_int]),
@@ -356,6 +378,9 @@ EXPORTS = {
     "nrnerf_query": (C.c_int, [C.c_void_p, C.POINTER(QueryArgs), C.c_void_p]),
     "nrnerf_grid_points": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "nrnerf_field_from_raw": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrnerf_isosurface_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "nrnerf_isosurface_count": (C.c_int, [C.POINTER(IsosurfaceArgs), C.c_void_p]),
+    "nrnerf_isosurface_emit": (C.c_int, [C.POINTER(IsosurfaceArgs), C.c_void_p]),
     "nrnerf_generate_rays": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
     "nrnerf_sample_depths": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "nrnerf_sample_depths_points": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

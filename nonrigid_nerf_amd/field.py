@@ -176,3 +176,209 @@ def sample_grid(render_kwargs, latent, min_point=None, max_point=None, resolutio
             _lib.check(lib.nrnerf_field_from_raw(raw.data_ptr(), ch, n * gx, sigma_rows[first:first + n].data_ptr(),
                                                  rgb_rows[first:first + n].data_ptr(), stream), "nrnerf_field_from_raw")
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# iso-surface meshes of the field (nrnerf_isosurface_count / _emit: marching tetrahedra on the device)
+# --------------------------------------------------------------------------------------------
+def isosurface(volume: torch.Tensor, level, min_point, max_point, *, normals=True):
+    """The iso-surface ``volume == level`` of a float32 volume ``[Gz, Gy, Gx]`` on the device (the layout of ``sample_grid``'s ``"sigma"``)
+    over the box ``[min_point, max_point]``, by marching tetrahedra over the Kuhn triangulation of every cell.
+
+    Returns ``{"vertices": float32 [V, 3], "faces": int32 [F, 3], "normals": float32 [V, 3]}`` (``normals`` only when asked for), on the
+    device.  A grid vertex is inside iff ``value >= level`` (NaN is outside); every triangle's normal points from inside to outside -- for a
+    density, towards lower density -- and ``normals`` is the unit ``-grad value`` at each vertex.  The mesh is closed away from the box faces,
+    shares one vertex per grid edge, keeps zero-area triangles (a value equal to the level), and has the same bytes on every run; the exact
+    definitions are in csrc/nrnerf_isosurface.h.  One host read -- the two totals, between the counting and the emitting pass -- is the only
+    synchronisation.  Raises ``Unsupported`` for a mesh of 2^31 or more vertices or triangles, or a grid beyond 2^30 vertices."""
+    if volume.device.type != "cuda":
+        raise R.Unsupported("the volume is not on a ROCm device")
+    if volume.dim() != 3:
+        raise ValueError(f"volume must be [Gz, Gy, Gx], got {tuple(volume.shape)}")
+    vol = volume.detach().to(torch.float32).contiguous()
+    gz, gy, gx = (int(v) for v in vol.shape)
+    if min(gx, gy, gz) < 1:
+        raise ValueError("every grid resolution must be >= 1")
+    lo, hi = grid_extent(min_point, max_point)
+    dev = vol.device
+    lib = _lib.load()
+    a = _lib.IsosurfaceArgs()
+    a.struct_size = C.sizeof(_lib.IsosurfaceArgs)
+    a.value, a.gx, a.gy, a.gz, a.level = vol.data_ptr(), gx, gy, gz, float(level)
+    a.min_point[:], a.max_point[:] = lo.tolist(), hi.tolist()
+    need = int(lib.nrnerf_isosurface_workspace_bytes(gx, gy, gz))
+    if need == 0 and min(gx, gy, gz) >= 2:
+        raise R.Unsupported(f"a grid of {gx} x {gy} x {gz} vertices is beyond the {_lib.ISO_MAX_VERTICES} the iso-surface kernels index")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    totals = torch.empty(2, dtype=torch.int64, device=dev)
+    a.workspace, a.workspace_bytes, a.totals = (ws.data_ptr() if need else None), need, totals.data_ptr()
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(lib.nrnerf_isosurface_count(C.byref(a), stream), "nrnerf_isosurface_count")
+        n_v, n_t = (int(v) for v in totals.tolist())                   # the one host read
+        if n_v >= 1 << 31 or n_t >= 1 << 31:
+            raise R.Unsupported(f"a mesh of {n_v} vertices and {n_t} triangles: faces are int32")
+        out = {"vertices": torch.empty((n_v, 3), dtype=torch.float32, device=dev), "faces": torch.empty((n_t, 3), dtype=torch.int32, device=dev)}
+        if normals:
+            out["normals"] = torch.empty((n_v, 3), dtype=torch.float32, device=dev)
+        a.vertices, a.faces = (out["vertices"].data_ptr() or None), (out["faces"].data_ptr() or None)
+        a.normals = (out["normals"].data_ptr() or None) if normals else None
+        a.n_vertices, a.n_triangles = n_v, n_t
+        _lib.check(lib.nrnerf_isosurface_emit(C.byref(a), stream), "nrnerf_isosurface_emit")
+    return out
+
+
+def density_along_rows(render_kwargs, latent, min_point, max_point, resolution, *, fine=True, precision=None, rows_per_launch=None):
+    """The density grid of a model whose points NO point query takes (exact Jacobian view directions, a bender that is not a compiled shape:
+    ``sample_grid`` raises ``Unsupported``), from the kernels that do take it -- the renderer's: every x-row of the grid is one ray from the
+    row's first vertex along ``(max_x - min_x, 0, 0)`` with near 0, far 1 and ``Gx`` samples, one coarse pass, and ``sigma = relu(raw sigma)`` of
+    its samples.  The samples are ``o + d * linspace(0, 1, Gx)`` in fp32: within a rounding of the grid's vertices in x, the same in y and z.
+    Returns float32 ``[Gz, Gy, Gx]``; needs ``Gx >= 2``."""
+    net = render_kwargs.get("network_fine") if fine and render_kwargs.get("network_fine") is not None else render_kwargs["network_fn"]
+    gx, gy, gz = grid_shape(resolution)
+    lo, hi = grid_extent(min_point, max_point)
+    if gx < 2:
+        raise R.Unsupported("a density grid along rays needs Gx >= 2")
+    dev = next(net.parameters()).device
+    if dev.type != "cuda":
+        dev = torch.device("cuda", torch.cuda.current_device())
+    model = R.get_model(net, None, precision=precision, device=dev)
+    dev = model.device
+    n_rows = gy * gz
+    lat = None
+    if model.needs_latents:
+        if latent is None:
+            raise ValueError("this model needs a latent code")
+        lat = torch.as_tensor(latent).to(device=dev, dtype=torch.float32).reshape(1, -1).contiguous()
+    cols = [torch.tensor([float(hi[0]) - float(lo[0]), 0.0, 0.0, 0.0, 1.0], dtype=torch.float32, device=dev)]
+    if getattr(net, "use_viewdirs", False):
+        cols.append(torch.tensor([1.0, 0.0, 0.0], dtype=torch.float32, device=dev))
+    tail = torch.cat(cols)
+    knobs = R._query_knobs(net)
+    sigma = torch.empty((gz, gy, gx), dtype=torch.float32, device=dev)
+    rows = sigma.view(n_rows, gx)
+    with torch.no_grad():
+        for first, n in plan_slabs(n_rows, default_rows_per_launch(gx) if rows_per_launch is None else rows_per_launch):
+            origins = grid_points(lo, hi, (1, gy, gz), first_row=first, n_rows=n, device=dev)[:, 0, :3]
+            rays = torch.cat([origins, tail.expand(n, -1)], -1).contiguous()
+            try:
+                out = model.render(rays, None if lat is None else lat.expand(n, -1), gx, 0, retraw=True,
+                                   rigidity_cutoff=knobs["rigidity_cutoff"], test_time_scaling=knobs["test_time_scaling"])
+            except _lib.NrnerfError as e:
+                if e.status != _lib.ERR_UNSUPPORTED:
+                    raise
+                raise R.Unsupported(str(e)) from e
+            rows[first:first + n] = field_from_raw(out["raw"])[0]
+    return sigma
+
+
+def vertex_probe_step(min_point, max_point, resolution) -> float:
+    """``h`` of ``extract_mesh``'s two-sample rows: one cell diagonal of the grid, rounded to float32.  Pure."""
+    g = grid_shape(resolution)
+    lo, hi = grid_extent(min_point, max_point)
+    step = [(float(hi[c]) - float(lo[c])) / (g[c] - 1) if g[c] > 1 else 0.0 for c in range(3)]
+    return float(np.float32(np.sqrt(sum(s * s for s in step))))
+
+
+def query_vertices(network, vertices, normals, latent=None, *, probe_step=None, precision=None):
+    """``query_points`` at mesh vertices under ``extract_mesh``'s view-direction rule -> ``(raw [V, C], details)``, each detail ``[V, .]``.
+    No view-dependent head: a flat query.  A head without bender: ``viewdirs = -normal``, one vertex per row.  A head behind a bender: rows
+    ``(v + probe_step * n, v)``, sample 1 -- its finite-difference direction (rnh:339-351) is that of a ray arriving along ``-normal``."""
+    n_v = int(vertices.shape[0])
+    views, has_bender = bool(getattr(network, "use_viewdirs", False)), R._bender_of(network) is not None
+    lat = None if latent is None else torch.as_tensor(latent).to(device=vertices.device, dtype=torch.float32).reshape(1, -1).contiguous()
+    rows_lat = None if lat is None else lat.expand(n_v, -1)
+    with torch.no_grad():
+        if not views:
+            return R.query_points(vertices.contiguous(), network, lat, None, detailed_output=True, precision=precision)
+        if has_bender:
+            if probe_step is None:
+                raise ValueError("a view-dependent head behind a ray bender needs probe_step")
+            rows = torch.stack([vertices + float(probe_step) * normals, vertices], 1).contiguous()        # [V, 2, 3]
+            raw, det = R.query_points(rows, network, rows_lat, None, detailed_output=True, precision=precision)
+            return raw[:, 1].contiguous(), {k: v[:, 1] for k, v in det.items()}
+        raw, det = R.query_points(vertices.reshape(n_v, 1, 3).contiguous(), network, rows_lat, (-normals).contiguous(), detailed_output=True,
+                                  precision=precision)
+        return raw[:, 0].contiguous(), {k: v[:, 0] for k, v in det.items()}
+
+
+def extract_mesh(render_kwargs, latent, level, min_point=None, max_point=None, resolution=128, *, fine=True, with_bending=True, colors=True,
+                 rigidity=True, precision=None, checkpoint=None, rows_per_launch=None):
+    """The density iso-surface ``sigma == level`` of one time step (``latent``) -- or of the canonical volume, ``with_bending=False`` -- as a
+    mesh with per-vertex attributes: ``sample_grid`` -> ``isosurface`` on ``"sigma"`` -> ``query_points`` at the mesh vertices, all on the device.
+
+    Returns ``{"vertices", "faces", "normals"}`` as ``isosurface`` does, plus ``"rgb"`` uint8 ``[V, 3]`` (``colors``: ``field_from_raw`` of the
+    query at the vertices) and ``"rigidity"`` float32 ``[V]`` (``rigidity``, only with a bender: the query's ``rigidity_mask``).  Vertices are in
+    the space the grid was sampled in: the observed space of that time step, or canonical space.  ``render_kwargs``, ``latent``, ``fine``, the
+    box (default: the checkpoint's volume extent), ``resolution``, ``precision`` and ``rows_per_launch`` are ``sample_grid``'s.
+
+    Colour of a view-dependent model: that of a ray ARRIVING along ``-normal`` (``query_vertices``).  What ``query_points`` cannot take --
+    exact (Jacobian) view directions, a bender that is not a compiled shape -- raises ``Unsupported``, unless ``colors=False, rigidity=False``
+    ask for the geometry alone: the density grid then comes from the renderer's kernels, ``density_along_rows``."""
+    net = render_kwargs.get("network_fine") if fine and render_kwargs.get("network_fine") is not None else render_kwargs["network_fn"]
+    if min_point is None or max_point is None:
+        from .visualize import volume_extent_of
+        ext = volume_extent_of(checkpoint) if checkpoint is not None else None
+        if ext is None:
+            raise ValueError("extract_mesh needs min_point / max_point (or a checkpoint that carries its volume extent)")
+        min_point, max_point = ext
+    g = grid_shape(resolution)
+    lo, hi = grid_extent(min_point, max_point)
+    query_net = net if with_bending else canonical_view(net)
+    has_bender = R._bender_of(query_net) is not None
+    attributes = bool(colors) or (bool(rigidity) and has_bender)
+    try:
+        sigma = sample_grid({"network_fn": net}, latent, lo, hi, g, fine=False, with_bending=with_bending, rows_per_launch=rows_per_launch,
+                            precision=precision)["sigma"]
+    except R.Unsupported:
+        if attributes:
+            raise
+        sigma = density_along_rows({"network_fn": query_net}, latent, lo, hi, g, fine=False, precision=precision, rows_per_launch=rows_per_launch)
+    mesh = isosurface(sigma, level, lo, hi, normals=True)
+    if not attributes:
+        return mesh
+    n_v, dev = int(mesh["vertices"].shape[0]), mesh["vertices"].device
+    if n_v == 0:
+        raw, det = torch.zeros((0, 4), device=dev), {"rigidity_mask": torch.zeros((0, 1), device=dev)}
+    else:
+        raw, det = query_vertices(query_net, mesh["vertices"], mesh["normals"], latent, probe_step=vertex_probe_step(lo, hi, g), precision=precision)
+    if colors:
+        mesh["rgb"] = field_from_raw(raw)[1] if n_v else torch.empty((0, 3), dtype=torch.uint8, device=dev)
+    if rigidity and has_bender:
+        mesh["rigidity"] = det["rigidity_mask"].reshape(n_v).contiguous()
+    return mesh
+
+
+def write_ply(path, mesh) -> None:
+    """``mesh`` (what ``isosurface`` / ``extract_mesh`` return; tensors or arrays) as a binary little-endian PLY: vertex properties ``x y z``
+    ``[nx ny nz]`` ``[red green blue]`` ``[rigidity]`` -- the bracketed ones when the mesh carries ``"normals"`` / ``"rgb"`` / ``"rigidity"`` --
+    and faces as ``uchar int vertex_indices``.  numpy only; the one place the mesh comes to the host."""
+    def host(v, dtype):
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        return np.ascontiguousarray(v, dtype=dtype)
+
+    verts = host(mesh["vertices"], "<f4").reshape(-1, 3)
+    faces = host(mesh["faces"], "<i4").reshape(-1, 3)
+    n_v = verts.shape[0]
+    fields, cols, header = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")], [verts[:, 0], verts[:, 1], verts[:, 2]], ["float x", "float y", "float z"]
+    if mesh.get("normals") is not None:
+        nrm = host(mesh["normals"], "<f4").reshape(n_v, 3)
+        for c, name in enumerate(("nx", "ny", "nz")):
+            fields.append((name, "<f4")); cols.append(nrm[:, c]); header.append(f"float {name}")
+    if mesh.get("rgb") is not None:
+        rgb = host(mesh["rgb"], "u1").reshape(n_v, 3)
+        for c, name in enumerate(("red", "green", "blue")):
+            fields.append((name, "u1")); cols.append(rgb[:, c]); header.append(f"uchar {name}")
+    if mesh.get("rigidity") is not None:
+        fields.append(("rigidity", "<f4")); cols.append(host(mesh["rigidity"], "<f4").reshape(n_v)); header.append("float rigidity")
+    vrec = np.empty(n_v, dtype=np.dtype(fields))            # packed: no padding between the properties
+    for (name, _), col in zip(fields, cols):
+        vrec[name] = col
+    frec = np.empty(faces.shape[0], dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+    frec["n"], frec["v"] = 3, faces
+    lines = ["ply", "format binary_little_endian 1.0", f"element vertex {n_v}"] + [f"property {h}" for h in header] + \
+            [f"element face {faces.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(lines) + "\n").encode("ascii"))
+        f.write(vrec.tobytes())
+        f.write(frec.tobytes())
