@@ -400,7 +400,9 @@ typedef struct nrnerf_trunk_args {
                                    contiguous (columns beyond the ray's end: finite padding) -- the operand layout of
                                    nrnerf_trunk_wgrad */
     void* relu_mask;            /* bf16 mode only: uint16 [depth][B][64 lanes][width/32], which values passed the relu; forward
-                                   writes, backward reads (instead of acts) */
+                                   writes, backward reads (instead of acts).  Lane 32 h + j holds sample j of the block; bit r of
+                                   its word t is feature 32 t + 4 h + (r & 3) + 8 (r >> 2) (the lane's accumulator register r of
+                                   tile t), set when the fp32 pre-activation is > 0 (tests/test_trunk_layers.py pins the map) */
     /* forward */
     float* raw4;                /* out [M,4]  rgb + sigma logits (what nrnerf_composite_* consume) */
     float* raw;                 /* out [M,raw_ch] all output channels ("raw" of render_rays), or NULL */
@@ -424,7 +426,8 @@ typedef struct nrnerf_trunk_args {
                                    back to the points), or the ray's own direction (train.py:73-76) */
     void* hv;                   /* relu(views_linears[0]([feature_linear(h), enc(dirs)])), width/2 values per sample, forward
                                    writes: float [M][width/2] (fp32 mode) or bf16 [B][width/2][32] */
-    void* hv_mask;              /* bf16 mode only: uint16 [B][64 lanes][width/64], relu bits of hv; forward writes, backward reads */
+    void* hv_mask;              /* bf16 mode only: uint16 [B][64 lanes][width/64], relu bits of hv (lane and bit map of relu_mask over
+                                   the width/2 features of hv); forward writes, backward reads */
     void* d_pre_v;              /* backward out: gradient wrt the views layer's pre-activation, type and layout of hv */
     float* d_dirs;              /* backward out [M,3]: gradient wrt dirs; NULL when nobody differentiates them (no bender) */
 } nrnerf_trunk_args;
