@@ -946,6 +946,54 @@ size_t nrnerf_isosurface_workspace_bytes(int32_t gx, int32_t gy, int32_t gz);
 int nrnerf_isosurface_count(const nrnerf_isosurface_args* args, void* hip_stream);
 int nrnerf_isosurface_emit(const nrnerf_isosurface_args* args, void* hip_stream);
 
+/* ---- ABI 10 (additions): the ray bender walked backwards -- canonical points to the observed space of a time step.
+ *
+ * The bender maps an observed point x of the time step with code l to canonical space, bend(x, l) = x + m(x) o(x, l) [test_time_scaling]
+ * (run_nerf_helpers.py:507-577).  nrnerf_bender_inverse solves bend(x, l) = c for x by the damped fixed-point iteration
+ *     x <- x - relaxation * (bend(x, l) - c),        x0 = `initial`, or c itself,
+ * per point, inside ONE kernel (csrc/nrnerf_bend_inverse.h): evaluate bend(x); the residual is
+ * r = max_c |bend(x)_c - c_c|; the point is finished when r <= tolerance or after max_iters evaluations, otherwise x is updated and
+ * evaluated again.  No update follows the last evaluation: `residual` is the residual OF `observed`, and `iterations` the evaluations made
+ * (1 .. max_iters).  A point is converged iff residual <= tolerance; the map is not a contraction everywhere (less so under
+ * test_time_scaling > 1), which is what relaxation < 1 is for.  A NaN point is never finished early: iterations = max_iters, residual NaN.
+ * bend(x) is evaluated with the arithmetic of nrnerf_query's fp32 bender step, bit for bit: nrnerf_query on `observed` (same code, same
+ * knobs) answers input_pts with max_c |input_pts_c - c_c| == residual exactly.  A point's result does not depend on the other points of
+ * the call, their order, the row shape, point_stride or the flags.
+ * fp32 handles only (a 16-bit bender rounds the point itself to 16 bits: a tolerance on bend(x) - c has no meaning there), bender
+ * architectures 5 x 64 and 7 x 64.  Device pointers only, asynchronous on the stream, allocates nothing.
+ * flags: NRNERF_RENDER_FIXED_SHARES (every wave takes a fixed share of the 32-point blocks instead of the next one from the work counter;
+ * same outputs) or 0.
+ * Checks, in this order: NRNERF_ERR_INVALID for a NULL model / record or a wrong struct_size; n_rows < 0, n_samples outside
+ * 1 .. NRNERF_MAX_SAMPLES, point_stride < 3, latent_stride < 0; tolerance < 0 or NaN; relaxation outside (0, 1]; max_iters outside
+ * 1 .. 1024; an unknown flag bit.  Then n_rows == 0 answers NRNERF_OK without a launch.  Then NRNERF_ERR_INVALID for NULL canonical /
+ * latents / observed, and for a model without ray bender (there is nothing to invert); NRNERF_ERR_UNSUPPORTED for a handle that is not fp32, a bender
+ * that is not one of the two compiled shapes, or 2^31 or more 32-point blocks; NRNERF_ERR_WORKSPACE for a NULL workspace, fewer than
+ * nrnerf_bender_inverse_workspace_bytes() bytes or a base that is not 256-byte aligned; and -- the first HIP calls -- NRNERF_ERR_INVALID for
+ * memory that is not device memory of the model's device. */
+typedef struct nrnerf_bender_inverse_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_bender_inverse_args) */
+    int32_t n_rows, n_samples;  /* N >= 0, 1 <= S <= NRNERF_MAX_SAMPLES; the latent code is per row */
+    const float* canonical;     /* [N, S, point_stride] canonical points c; 16-byte loads when point_stride == 4 and the base is aligned */
+    int32_t point_stride;       /* >= 3 */
+    const float* initial;       /* [N, S, point_stride] first guess x0, or NULL: the canonical point itself */
+    const float* latents;       /* [N, latent_size] deformation codes */
+    int32_t latent_stride;      /* floats between rows; 0 = one code for the call */
+    int32_t has_rigidity_cutoff;    float rigidity_cutoff;      /* the knobs are part of the map that is inverted */
+    int32_t has_test_time_scaling;  float test_time_scaling;
+    float tolerance;            /* >= 0, absolute, on max_c |bend(x)_c - c_c|; 0 = run to max_iters or an exact hit */
+    float relaxation;           /* omega, 0 < omega <= 1 */
+    int32_t max_iters;          /* 1 .. 1024 */
+    uint32_t flags;             /* NRNERF_RENDER_FIXED_SHARES or 0 */
+    float* observed;            /* out [N, S, 3] */
+    float* residual;            /* out [N, S] residual of `observed`, or NULL */
+    int32_t* iterations;        /* out [N, S] evaluations made, 1 .. max_iters, or NULL */
+    void* workspace;            /* >= nrnerf_bender_inverse_workspace_bytes(), 256-byte aligned: the work counter, zeroed by the call on the stream (untouched under FIXED_SHARES) */
+    size_t workspace_bytes;
+} nrnerf_bender_inverse_args;
+/* 256 for a handle nrnerf_bender_inverse takes, 0 otherwise (NULL, no bender, not fp32, not a compiled bender shape) */
+size_t nrnerf_bender_inverse_workspace_bytes(const nrnerf_model* model);
+int nrnerf_bender_inverse(const nrnerf_model* model, const nrnerf_bender_inverse_args* args, void* hip_stream);
+
 /* Host-only packing (no device needed): writes the MFMA-fragment weight stream + unit table + bias
  * table of one pass exactly as nrnerf_model_create uploads them.  which: 0 = coarse, 1 = fine, 2 = fine without the
  * bender layers, 3 = bender + rigidity layers alone (2, 3: the split-bender path; need a bender and not the exact view directions),

@@ -336,6 +336,22 @@ class IsosurfaceArgs(C.Structure):
                 ("n_vertices", C.c_int64), ("n_triangles", C.c_int64)]
 
 
+class BenderInverseArgs(C.Structure):
+    """nrnerf_bender_inverse_args (ABI 10 additions): canonical points -> observed points of a time step, the damped fixed-point iteration."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_rows", C.c_int32), ("n_samples", C.c_int32),
+                ("canonical", C.c_void_p), ("point_stride", C.c_int32), ("initial", C.c_void_p),
+                ("latents", C.c_void_p), ("latent_stride", C.c_int32),
+                ("has_rigidity_cutoff", C.c_int32), ("rigidity_cutoff", C.c_float),
+                ("has_test_time_scaling", C.c_int32), ("test_time_scaling", C.c_float),
+                ("tolerance", C.c_float), ("relaxation", C.c_float), ("max_iters", C.c_int32), ("flags", C.c_uint32),
+                ("observed", C.c_void_p), ("residual", C.c_void_p), ("iterations", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+BENDER_INVERSE_FLAGS = RENDER_FIXED_SHARES      # the one render flag nrnerf_bender_inverse honours; any other bit: INVALID
+BENDER_INVERSE_MAX_ITERS = 1024
+
+
 ISO_BLOCK, ISO_SCAN_CHUNK, ISO_MAX_VERTICES = 256, 4096, 1 << 30      # csrc/nrnerf_isosurface.h
 
 
@@ -381,6 +397,8 @@ EXPORTS = {
     "nrnerf_isosurface_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "nrnerf_isosurface_count": (C.c_int, [C.POINTER(IsosurfaceArgs), C.c_void_p]),
     "nrnerf_isosurface_emit": (C.c_int, [C.POINTER(IsosurfaceArgs), C.c_void_p]),
+    "nrnerf_bender_inverse_workspace_bytes": (C.c_size_t, [C.c_void_p]),
+    "nrnerf_bender_inverse": (C.c_int, [C.c_void_p, C.POINTER(BenderInverseArgs), C.c_void_p]),
     "nrnerf_generate_rays": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
     "nrnerf_sample_depths": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "nrnerf_sample_depths_points": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -349,6 +349,148 @@ def extract_mesh(render_kwargs, latent, level, min_point=None, max_point=None, r
     return mesh
 
 
+# --------------------------------------------------------------------------------------------
+# the bender walked backwards (nrnerf_bender_inverse): canonical points -> the observed space of a time step
+# --------------------------------------------------------------------------------------------
+def unbend_points(network, canonical_points, latent, *, initial=None, tol=1e-6, relaxation=1.0, max_iters=64, flags=None):
+    """The observed points ``x`` of a time step whose bent image is ``canonical_points``: ``bend(x, latent) = c``, solved per point by the
+    damped fixed-point iteration ``x <- x - relaxation (bend(x) - c)`` inside one kernel (``Model.bender_inverse``).
+
+    ``canonical_points``: ``[N, S, 3]`` with ``latent [N, latent_size]`` (a code per row), or a flat ``[M, 3]`` with ONE code (``[latent_size]`` or
+    ``[1, latent_size]``; laid out as rows by ``plan_flat_rows``, as ``query_points`` does).  ``initial``: a first guess of the same shape
+    (default: the canonical points).  A point is finished when ``max_c |bend(x)_c - c_c| <= tol`` or after ``max_iters`` (1 .. 1024)
+    evaluations; ``0 < relaxation <= 1`` -- the map is not a contraction everywhere, less so under ``test_time_scaling > 1``, and a smaller
+    factor then converges where 1 oscillates.  The knobs (``rigidity_test_time_cutoff``, ``test_time_scaling``) are read from the bender as
+    ``query_points`` reads them: they are part of the map.
+
+    Returns ``{"points", "residual", "iterations", "converged"}``: ``[N, S, 3]`` / ``[N, S]`` (flat: ``[M, 3]`` / ``[M]``); ``residual`` is that
+    OF the returned point -- ``query_points(points, detailed_output=True)["input_pts"]`` on the fp32 handle differs from ``canonical_points`` by
+    exactly it -- ``iterations`` (int32) the evaluations made, ``converged = residual <= tol``.  Always the FP32 handle of the network, whatever
+    precision is selected for rendering: a 16-bit bender rounds the point itself.  A network without bender returns the points themselves
+    (``iterations`` 0, all converged).  Raises ``Unsupported`` for a bender shape without a compiled kernel, and under autograd."""
+    pts = canonical_points
+    if pts.device.type != "cuda":
+        raise R.Unsupported("points are not on a ROCm device")
+    lat_t = latent if torch.is_tensor(latent) else None
+    if R._trains(network, None, pts, lat_t) or (initial is not None and torch.is_grad_enabled() and initial.requires_grad):
+        raise R.Unsupported("autograd is enabled (the inverse has no gradient)")
+    flat = pts.dim() == 2
+    if pts.dim() not in (2, 3) or pts.shape[-1] != 3:
+        raise ValueError(f"canonical_points must be [N, S, 3] or [M, 3], got {tuple(pts.shape)}")
+    if initial is not None and tuple(initial.shape) != tuple(pts.shape):
+        raise ValueError(f"initial must have the shape of canonical_points {tuple(pts.shape)}, got {tuple(initial.shape)}")
+    dev = pts.device
+    if R._bender_of(network) is None:
+        p = pts.detach().to(torch.float32).clone()
+        return {"points": p, "residual": torch.zeros(p.shape[:-1], dtype=torch.float32, device=dev),
+                "iterations": torch.zeros(p.shape[:-1], dtype=torch.int32, device=dev),
+                "converged": torch.ones(p.shape[:-1], dtype=torch.bool, device=dev)}
+    if latent is None:
+        raise ValueError("a ray bender needs a latent code")
+    lat = torch.as_tensor(latent).detach().to(device=dev, dtype=torch.float32)
+    pts = pts.detach()
+    init = None if initial is None else initial.detach()
+    if flat:
+        M = int(pts.shape[0])
+        n_rows, row, n_pad = R.plan_flat_rows(M)
+        if lat.dim() == 1:
+            lat = lat[None]
+        if lat.dim() != 2 or lat.shape[0] != 1:
+            raise ValueError("flat points take one latent code [1, latent_size]")
+        lat = lat.contiguous().expand(n_rows, -1)
+
+        def rows(t):
+            if n_pad:
+                t = torch.cat([t, t[-1:].expand(n_pad, -1)], 0)
+            return t.reshape(n_rows, row, 3)
+        pts = rows(pts)
+        init = None if init is None else rows(init)
+    model = R.get_model(network, None, precision="f32", device=dev)
+    knobs = R._query_knobs(network)
+    try:
+        x, res, its = model.bender_inverse(pts, lat, init, tol=tol, relaxation=relaxation, max_iters=max_iters,
+                                           rigidity_cutoff=knobs["rigidity_cutoff"], test_time_scaling=knobs["test_time_scaling"], flags=flags)
+    except _lib.NrnerfError as e:
+        if e.status != _lib.ERR_UNSUPPORTED:
+            raise
+        raise R.Unsupported(str(e)) from e
+    if flat:
+        x, res, its = x.reshape(-1, 3)[:M], res.reshape(-1)[:M], its.reshape(-1)[:M]
+    return {"points": x, "residual": res, "iterations": its, "converged": res <= float(np.float32(tol))}
+
+
+def vertex_normals(vertices, faces):
+    """Area-weighted unit vertex normals of a triangle mesh, with torch ops on the tensors' device: the sum over a vertex's triangles of
+    ``(v1 - v0) x (v2 - v0)`` (twice the area times the face normal), normalised.  Orientation follows the faces' winding -- for ``isosurface``'s
+    faces, from inside to outside.  A vertex of no triangle, or of zero-area ones only, gets the zero vector.  ``[V, 3]`` float32."""
+    v = vertices.to(torch.float32)
+    f = faces.to(torch.int64)
+    acc = torch.zeros_like(v)
+    if f.numel():
+        v0, v1, v2 = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+        fn = torch.cross(v1 - v0, v2 - v0, dim=-1)
+        acc.index_put_((f.t().reshape(-1),), fn.repeat(3, 1), accumulate=True)
+    length = acc.norm(dim=-1, keepdim=True)
+    return torch.where(length > 0, acc / length.clamp_min(1e-30), torch.zeros_like(acc))
+
+
+def animate_mesh(canonical_mesh, render_kwargs, latents, *, fine=True, warm_start=True, **solver):
+    """A canonical mesh carried into every time step: ONE connectivity, the vertices moved by the inverse of the ray bender.
+
+    ``canonical_mesh``: what ``extract_mesh(..., with_bending=False)`` returns.  ``latents``: the codes of the frames, ``[T, latent_size]`` (or a
+    sequence of codes).  ``solver``: ``tol`` / ``relaxation`` / ``max_iters`` / ``flags`` of ``unbend_points``.  With ``warm_start`` frame t's
+    solution is frame t + 1's first guess (neighbouring time steps deform alike: most vertices then finish in one or two evaluations).
+
+    Returns one mesh per code, ``{"vertices", "normals", "converged", "residual", "faces"[, "rgb"][, "rigidity"]}``: ``faces`` / ``rgb`` /
+    ``rigidity`` are the canonical mesh's own tensors, shared by every frame, and ``normals = vertex_normals`` of the moved vertices -- every
+    frame has the same vertex count and connectivity, and ``write_ply`` takes a frame as it is."""
+    net = render_kwargs.get("network_fine") if fine and render_kwargs.get("network_fine") is not None else render_kwargs["network_fn"]
+    verts = canonical_mesh["vertices"].detach().to(torch.float32).contiguous()
+    faces = canonical_mesh["faces"]
+    codes = [latents[t] for t in range(len(latents))]
+    shared = {key: canonical_mesh[key] for key in ("rgb", "rigidity") if canonical_mesh.get(key) is not None}
+    out, guess = [], None
+    with torch.no_grad():
+        for code in codes:
+            if verts.shape[0] == 0:
+                sol = {"points": verts.clone(), "residual": verts.new_zeros((0,)), "converged": torch.ones((0,), dtype=torch.bool, device=verts.device)}
+            else:
+                sol = unbend_points(net, verts, torch.as_tensor(code).reshape(1, -1), initial=guess, **solver)
+            if warm_start:
+                guess = sol["points"]
+            out.append({"vertices": sol["points"], "normals": vertex_normals(sol["points"], faces), "converged": sol["converged"],
+                        "residual": sol["residual"], "faces": faces, **shared})
+    return out
+
+
+def track_points(render_kwargs, points, latent_from, latents_to, *, fine=True, **solver):
+    """Points seen in one time step found again in others: ``points [M, 3]`` of the observed space of ``latent_from`` are bent to canonical
+    space (``query_points(..., detailed_output=True)``'s ``input_pts`` on the fp32 handle) and from there carried into each code of
+    ``latents_to`` by one ``unbend_points`` call (``solver``: its ``tol`` / ``relaxation`` / ``max_iters`` / ``flags``).
+
+    Returns ``{"canonical": [M, 3], "tracks": [{"points", "residual", "iterations", "converged"}, ...]}``, one entry per target code."""
+    net = render_kwargs.get("network_fine") if fine and render_kwargs.get("network_fine") is not None else render_kwargs["network_fn"]
+    if points.dim() != 2 or points.shape[-1] != 3:
+        raise ValueError(f"points must be [M, 3], got {tuple(points.shape)}")
+    with torch.no_grad():
+        pts = points.detach().to(torch.float32).contiguous()
+        if R._bender_of(net) is None:
+            canonical = pts.clone()
+        else:
+            # rows of 64 (the bent point of a sample does not depend on its row; a view-dependent head behind a bender refuses flat input)
+            M = int(pts.shape[0])
+            n_rows, row, n_pad = R.plan_flat_rows(M)
+            rows = torch.cat([pts, pts[-1:].expand(n_pad, -1)], 0) if n_pad else pts
+            lat = torch.as_tensor(latent_from).to(device=pts.device, dtype=torch.float32).reshape(1, -1).contiguous()
+            if M == 0:
+                canonical = pts.clone()
+            else:
+                det = R.query_points(rows.reshape(n_rows, row, 3), net, lat.expand(n_rows, -1), None, detailed_output=True, precision="f32")[1]
+                canonical = det["input_pts"].reshape(-1, 3)[:M].contiguous()
+        tracks = [unbend_points(net, canonical, torch.as_tensor(latents_to[t]).reshape(1, -1), **solver) for t in range(len(latents_to))]
+    return {"canonical": canonical, "tracks": tracks}
+
+
 def write_ply(path, mesh) -> None:
     """``mesh`` (what ``isosurface`` / ``extract_mesh`` return; tensors or arrays) as a binary little-endian PLY: vertex properties ``x y z``
     ``[nx ny nz]`` ``[red green blue]`` ``[rigidity]`` -- the bracketed ones when the mesh carries ``"normals"`` / ``"rgb"`` / ``"rigidity"`` --

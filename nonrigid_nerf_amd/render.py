@@ -582,6 +582,59 @@ class Model:
         raw = got.pop("raw")
         return (raw, got) if detailed_output else raw
 
+    def bender_inverse(self, canonical: torch.Tensor, latents: torch.Tensor, initial: torch.Tensor | None = None, *, tol: float = 1e-6,
+                       relaxation: float = 1.0, max_iters: int = 64, rigidity_cutoff=None, test_time_scaling=None, flags: int | None = None):
+        """``nrnerf_bender_inverse``: for canonical points ``[N, S, 3 | 4]`` and the codes ``latents [N, latent_size]`` (or one row, stride 0)
+        the observed points ``x`` with ``bend(x) = canonical``, by the damped fixed-point iteration ``x <- x - relaxation (bend(x) - c)`` from
+        ``initial`` (same shape as ``canonical``; default: the canonical points), all inside one kernel.  Returns ``(points [N, S, 3],
+        residual [N, S], iterations int32 [N, S])``: the residual ``max_c |bend(x)_c - c_c|`` OF the returned point and the evaluations made.
+        An fp32 handle only (``NrnerfError`` with ``ERR_UNSUPPORTED`` otherwise)."""
+        if canonical.dim() != 3 or canonical.shape[-1] not in (3, 4):
+            raise ValueError(f"canonical points must have shape (N, S, 3) or (N, S, 4), got {tuple(canonical.shape)}")
+        N, S = int(canonical.shape[0]), int(canonical.shape[1])
+        if not 1 <= S <= _lib.MAX_SAMPLES:
+            raise ValueError(f"1 <= samples per row <= {_lib.MAX_SAMPLES}, got {S}")
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        canonical = canonical.to(**f32).contiguous()
+        a = _lib.BenderInverseArgs()
+        a.struct_size = C.sizeof(_lib.BenderInverseArgs)
+        a.n_rows, a.n_samples = N, S
+        a.canonical, a.point_stride = canonical.data_ptr(), int(canonical.shape[-1])
+        if initial is not None:
+            if tuple(initial.shape) != tuple(canonical.shape):
+                raise ValueError(f"initial must have the shape of the canonical points {tuple(canonical.shape)}, got {tuple(initial.shape)}")
+            initial = initial.to(**f32).contiguous()
+            a.initial = initial.data_ptr()
+        if latents is None:
+            raise ValueError("ray_bending_latents are required")
+        if latents.dim() != 2 or latents.shape[0] != N or latents.shape[1] != self.latent_size:
+            raise ValueError(f"ray_bending_latents must have shape ({N}, {self.latent_size}), got {tuple(latents.shape)}")
+        if latents.stride(0) == 0 and latents.stride(1) == 1 and latents.dtype == torch.float32 and latents.device == dev:
+            a.latents, a.latent_stride = latents.data_ptr(), 0           # one code for the call
+        else:
+            latents = latents.to(**f32).contiguous()
+            a.latents, a.latent_stride = latents.data_ptr(), latents.shape[1]
+        a.tolerance, a.relaxation, a.max_iters = float(tol), float(relaxation), int(max_iters)
+        a.flags = (_lib.render_flags_from_env() & _lib.BENDER_INVERSE_FLAGS) if flags is None else int(flags)
+        if rigidity_cutoff is not None:
+            a.has_rigidity_cutoff, a.rigidity_cutoff = 1, float(rigidity_cutoff)
+        if test_time_scaling is not None:
+            a.has_test_time_scaling, a.test_time_scaling = 1, float(test_time_scaling)
+        points = torch.empty((N, S, 3), **f32)
+        residual = torch.empty((N, S), **f32)
+        iterations = torch.empty((N, S), dtype=torch.int32, device=dev)
+        a.observed, a.residual, a.iterations = (points.data_ptr() or None), (residual.data_ptr() or None), (iterations.data_ptr() or None)
+        nbytes = self.lib.nrnerf_bender_inverse_workspace_bytes(self.handle)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            ws = self._workspace(nbytes + 256, stream)
+            a.workspace, a.workspace_bytes = (ws.data_ptr() + 255) // 256 * 256, nbytes
+            _lib.check(self.lib.nrnerf_bender_inverse(self.handle, C.byref(a), C.c_void_p(stream)), "nrnerf_bender_inverse")
+            if N > 0:
+                self.note_use(dev)
+        return points, residual, iterations
+
     def note_use(self, dev=None):
         """Kernels reading this handle's weights were just queued on the current stream: remember an event there, so that
         a later weight refresh issued from ANOTHER stream can order itself after them (update_from_device).  The

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""No matrix instruction under a SAVED exec mask in the 16x16x32 kernels (csrc/build/nrnerf_net_x16*.o, nrnerf_gx16_w*.o, nrnerf_bend_x16.o).
+"""No matrix instruction under a SAVED exec mask in the 16x16x32 kernels (csrc/build/nrnerf_net_x16*.o, nrnerf_gx16_w*.o, nrnerf_bend_x16.o)
+and in the inverse bender (nrnerf_bend_inverse.o: a data-dependent loop around the fp32 bender's layers).
 
 The layers of these kernels read their weight fragments with `asm volatile` LDS reads that do not name the exec mask, so a lane-divergent
 region (`s_and_saveexec_b64 … s_or_b64 exec, exec, …`) that the compiler stretches over a layer would run it for some lanes only -- round 6
@@ -20,7 +21,7 @@ import check_isa  # noqa: E402
 def offending_regions(build_dir):
     out = []
     objs = sorted(glob.glob(os.path.join(build_dir, "nrnerf_net_x16*.o")) + glob.glob(os.path.join(build_dir, "nrnerf_gx16_w*.o")) +
-                  glob.glob(os.path.join(build_dir, "nrnerf_bend_x16.o")))
+                  glob.glob(os.path.join(build_dir, "nrnerf_bend_x16.o")) + glob.glob(os.path.join(build_dir, "nrnerf_bend_inverse.o")))
     for obj in objs:
         with tempfile.TemporaryDirectory() as tmp:
             co = check_isa.device_code_object(obj, tmp)
