@@ -994,6 +994,95 @@ typedef struct nrnerf_bender_inverse_args {
 size_t nrnerf_bender_inverse_workspace_bytes(const nrnerf_model* model);
 int nrnerf_bender_inverse(const nrnerf_model* model, const nrnerf_bender_inverse_args* args, void* hip_stream);
 
+/* ---- ABI 10 (additions): baked volumes of the field, rendered through the ray bender.
+ *
+ * The canonical volume does not depend on time: every time step is "bend the samples, then look the canonical field up".  A volume baked
+ * once from nrnerf_query's raw rows therefore serves every frame: nrnerf_bend_points bends the samples of a frame (the first half of
+ * nrnerf_query, no trunk pass), nrnerf_volume_render looks them up and composites them (csrc/nrnerf_volume.h).
+ *
+ * THE VOLUME.  The grid is that of nrnerf_grid_points: vertex-centred, p_c = min_c + i_c (max_c - min_c) / (G_c - 1), 2 <= G_c, at most 2^30
+ * vertices.  Storage: row-major raw [Gz, Gy, Gx, 4] = the network's (r, g, b, sigma) LOGITS -- before the sigmoid and the relu, the first four
+ * channels of nrnerf_query's raw rows -- as float32 (16 bytes per vertex) or IEEE half (8 bytes per vertex), the base aligned to one vertex.
+ * THE VALUE AT A POINT p, all in fp32, every operation rounded once:
+ *     s_c = (float)(G_c - 1) / (max_c - min_c);    g_c = (p_c - min_c) * s_c
+ *     any g_c NaN, < 0 or > G_c - 1:  the sample is EMPTY, raw = (0, 0, 0, 0) -- sigma 0 after the relu, a weight of exactly 0
+ *     else  i_c = min(floor(g_c), G_c - 2),  f_c = g_c - i_c,  and per channel the trilinear interpolation of the eight corners
+ *     (i_x + {0,1}, i_y + {0,1}, i_z + {0,1}) along x, then y, then z with  lerp(a, b, f) = fma(f, b, fma(-f, a, a)):
+ *     f = 0 returns a and f = 1 returns b bit for bit, so a point on a vertex of a grid it hits exactly returns the stored value.
+ * Half storage is widened to fp32 before any arithmetic.  tests/volume_reference.py states the same rule in float64.
+ *
+ * nrnerf_volume_render: per ray the S samples' logits from the volume, then the compositing of nrnerf_render / nrnerf_composite_forward
+ * (raw2outputs, train.py:724-789; the same device function, so the same bits as nrnerf_composite_forward on the `raw` output).  Sample i of ray
+ * n is points4[n, i, 0..2] (e.g. nrnerf_bend_points' bent4), or without points4 o + d z with the product rounded before the sum, as
+ * nrnerf_sample_depths_points rounds; z = the caller's depths, or the coarse spacing between the ray's near and far (`lindisp` honoured) as in
+ * nrnerf_composite_args.  The rays give the direction for dists * |d| and, without z, near / far.  removal_threshold: the sigma logit of a
+ * sample is multiplied by 0 where points4[n, i, 3] >= threshold (rnh:308-311).  The surface outputs are the reduction of nrnerf_render over
+ * points4: the sample whose accumulated weight is closest to 0.5, its point and its points4.w.  With rgb, disp and acc all NULL nothing is
+ * composited: `raw` alone is written (the lookup by itself).  One kernel, no atomics, no device counter: the same bits on every run.
+ * Device pointers only, asynchronous on the stream, allocates nothing, needs no workspace; runs on the device that owns rgb (raw when nothing
+ * is composited).
+ * Checks, in this order: NRNERF_ERR_INVALID for a NULL record or a wrong struct_size; n_rays < 0, n_samples outside 1 .. NRNERF_MAX_SAMPLES,
+ * ray_stride < 8; a g < 2, a max_c that is not > min_c (NaN included), an unknown volume_dtype.  NRNERF_ERR_UNSUPPORTED for more than 2^30
+ * vertices or 2^31 or more samples.  Then n_rays == 0 answers NRNERF_OK without a launch.  Then NRNERF_ERR_INVALID for a NULL rays / volume;
+ * rgb, disp, acc neither all given nor all NULL; nothing to write (no maps and no raw); weights / alpha / a surface output without the maps;
+ * a removal threshold or a surface output without points4; and -- the first HIP calls -- memory that is not device memory of one device. */
+enum { NRNERF_VOLUME_F32 = 0, NRNERF_VOLUME_F16 = 1 };
+typedef struct nrnerf_volume_render_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_volume_render_args) */
+    int32_t n_rays, n_samples;  /* N >= 0, 1 <= S <= NRNERF_MAX_SAMPLES */
+    const float* rays;          /* [N, ray_stride]: o (0..2), d (3..5), near, far (6, 7) */
+    int32_t ray_stride;         /* >= 8 */
+    int32_t lindisp;            /* the coarse spacing linear in inverse depth; read when z is NULL */
+    const float* z;             /* [N, S] sample depths, or NULL: the coarse spacing */
+    const float* points4;       /* [N, S, 4] sample points (xyz, rigidity), 16-byte aligned, or NULL: o + d z */
+    const void* volume;         /* [gz, gy, gx, 4] logits, float32 or half */
+    int32_t volume_dtype;       /* NRNERF_VOLUME_F32 / NRNERF_VOLUME_F16 */
+    int32_t g[3];               /* gx, gy, gz, each >= 2 */
+    float min_point[3];         /* the box, as in nrnerf_grid_points; max_c > min_c */
+    float max_point[3];
+    int32_t white_bkgd;
+    int32_t has_removal_threshold; float removal_threshold;
+    float* rgb;                 /* out [N, 3] */
+    float* disp;                /* out [N] */
+    float* acc;                 /* out [N] */
+    float* raw;                 /* out [N, S, 4] the sampled logits (after the removal knob), or NULL */
+    float* weights;             /* out [N, S] or NULL */
+    float* alpha;               /* out [N, S] or NULL */
+    float* surface_pts;         /* out [N, 3] or NULL */
+    float* surface_rigidity;    /* out [N] or NULL */
+    int32_t* median_index;      /* out [N] or NULL */
+} nrnerf_volume_render_args;
+int nrnerf_volume_render(const nrnerf_volume_render_args* args, void* hip_stream);
+
+/* nrnerf_bend_points: the bender step of nrnerf_query by itself -- the point-source stand-alone bender on points [N, S, point_stride], a code
+ * per row, to bent4 [N, S, 4] = (bent xyz, rigidity mask).  Kernel, weight image, precision, flags (NRNERF_RENDER_NO_X16,
+ * NRNERF_RENDER_BENDER_32X32, NRNERF_RENDER_FIXED_SHARES; any other bit is NRNERF_ERR_INVALID) and work counters are those nrnerf_query would
+ * take on the same handle, so bent4 holds the bits of its input_pts / rigidity_mask.  The workspace holds only the work counters, zeroed by
+ * the call on the stream when the launch takes them.  Nothing is recorded into the handle's profile.
+ * Checks, in this order: NRNERF_ERR_INVALID for a NULL model / record or a wrong struct_size; n_rows < 0, n_samples outside
+ * 1 .. NRNERF_MAX_SAMPLES, point_stride < 3, latent_stride < 0; an unknown flag bit.  Then n_rows == 0 answers NRNERF_OK without a launch.
+ * Then NRNERF_ERR_INVALID for NULL points / latents / bent4 and for a model without ray bender; NRNERF_ERR_UNSUPPORTED for a bender that is
+ * not one of the two compiled shapes (5 x 64, 7 x 64) or 2^31 or more samples / sample blocks; NRNERF_ERR_WORKSPACE for a NULL workspace, fewer
+ * than nrnerf_bend_points_workspace_bytes() bytes or a base that is not 256-byte aligned; and -- the first HIP calls -- NRNERF_ERR_INVALID for
+ * memory that is not device memory of the model's device. */
+typedef struct nrnerf_bend_points_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_bend_points_args) */
+    int32_t n_rows, n_samples;  /* N >= 0, 1 <= S <= NRNERF_MAX_SAMPLES; the latent code is per row */
+    const float* points;        /* [N, S, point_stride]; 16-byte loads when point_stride == 4 and the base is aligned */
+    int32_t point_stride;       /* >= 3 */
+    int32_t latent_stride;      /* floats between the rows of `latents`; 0 = one code for the call */
+    const float* latents;       /* [N, latent_size] deformation codes */
+    int32_t has_rigidity_cutoff;    float rigidity_cutoff;      /* the knobs of nrnerf_render_args */
+    int32_t has_test_time_scaling;  float test_time_scaling;
+    uint32_t flags;             /* bits of nrnerf_render_flags, see above */
+    float* bent4;               /* out [N, S, 4], 16-byte aligned */
+    void* workspace;            /* >= nrnerf_bend_points_workspace_bytes(), 256-byte aligned */
+    size_t workspace_bytes;
+} nrnerf_bend_points_args;
+/* 32768 (512 work counters, 64 bytes apart) for a handle nrnerf_bend_points takes, 0 otherwise (NULL, no bender, not a compiled bender shape) */
+size_t nrnerf_bend_points_workspace_bytes(const nrnerf_model* model);
+int nrnerf_bend_points(const nrnerf_model* model, const nrnerf_bend_points_args* args, void* hip_stream);
+
 /* Host-only packing (no device needed): writes the MFMA-fragment weight stream + unit table + bias
  * table of one pass exactly as nrnerf_model_create uploads them.  which: 0 = coarse, 1 = fine, 2 = fine without the
  * bender layers, 3 = bender + rigidity layers alone (2, 3: the split-bender path; need a bender and not the exact view directions),

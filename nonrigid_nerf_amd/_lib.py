@@ -352,6 +352,36 @@ BENDER_INVERSE_FLAGS = RENDER_FIXED_SHARES      # the one render flag nrnerf_ben
 BENDER_INVERSE_MAX_ITERS = 1024
 
 
+class VolumeRenderArgs(C.Structure):
+    """nrnerf_volume_render_args (ABI 10 additions): a baked volume of logits looked up at the samples of the rays and composited."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_rays", C.c_int32), ("n_samples", C.c_int32),
+                ("rays", C.c_void_p), ("ray_stride", C.c_int32), ("lindisp", C.c_int32),
+                ("z", C.c_void_p), ("points4", C.c_void_p),
+                ("volume", C.c_void_p), ("volume_dtype", C.c_int32), ("g", C.c_int32 * 3),
+                ("min_point", C.c_float * 3), ("max_point", C.c_float * 3),
+                ("white_bkgd", C.c_int32), ("has_removal_threshold", C.c_int32), ("removal_threshold", C.c_float),
+                ("rgb", C.c_void_p), ("disp", C.c_void_p), ("acc", C.c_void_p),
+                ("raw", C.c_void_p), ("weights", C.c_void_p), ("alpha", C.c_void_p),
+                ("surface_pts", C.c_void_p), ("surface_rigidity", C.c_void_p), ("median_index", C.c_void_p)]
+
+
+VOLUME_F32, VOLUME_F16 = 0, 1               # NRNERF_VOLUME_F32 / NRNERF_VOLUME_F16
+VOLUME_MAX_VERTICES = 1 << 30
+
+
+class BendPointsArgs(C.Structure):
+    """nrnerf_bend_points_args (ABI 10 additions): the bender step of nrnerf_query by itself, points -> bent4 (bent xyz, rigidity)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_rows", C.c_int32), ("n_samples", C.c_int32),
+                ("points", C.c_void_p), ("point_stride", C.c_int32), ("latent_stride", C.c_int32), ("latents", C.c_void_p),
+                ("has_rigidity_cutoff", C.c_int32), ("rigidity_cutoff", C.c_float),
+                ("has_test_time_scaling", C.c_int32), ("test_time_scaling", C.c_float),
+                ("flags", C.c_uint32), ("bent4", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+BEND_POINTS_WORKSPACE_BYTES = 512 * 64      # the work counters of the 16x16x32 point-source bender
+
+
 ISO_BLOCK, ISO_SCAN_CHUNK, ISO_MAX_VERTICES = 256, 4096, 1 << 30      # csrc/nrnerf_isosurface.h
 
 
@@ -399,6 +429,9 @@ EXPORTS = {
     "nrnerf_isosurface_emit": (C.c_int, [C.POINTER(IsosurfaceArgs), C.c_void_p]),
     "nrnerf_bender_inverse_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "nrnerf_bender_inverse": (C.c_int, [C.c_void_p, C.POINTER(BenderInverseArgs), C.c_void_p]),
+    "nrnerf_volume_render": (C.c_int, [C.POINTER(VolumeRenderArgs), C.c_void_p]),
+    "nrnerf_bend_points_workspace_bytes": (C.c_size_t, [C.c_void_p]),
+    "nrnerf_bend_points": (C.c_int, [C.c_void_p, C.POINTER(BendPointsArgs), C.c_void_p]),
     "nrnerf_generate_rays": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),
     "nrnerf_sample_depths": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "nrnerf_sample_depths_points": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),

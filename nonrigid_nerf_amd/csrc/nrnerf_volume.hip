@@ -1,0 +1,179 @@
+// nrnerf_volume.hip -- a baked volume of the field rendered by lookup: per sample the trilinear interpolation of the volume's (r, g, b, sigma)
+// logits at the sample's (bent) point, then the alpha compositing of nrnerf_composite_ray.h.  The sampling rule is stated in include/nrnerf.h
+// ("baked volumes") and, in float64, in tests/volume_reference.py; layout, resources and measurements: DESIGN.md section 3.13.
+//
+// volume_render_kernel<EPL, HALF>: one wave per ray at a time, rays handed out by a grid-stride loop (no atomics, no device counter: the same
+// bits on every run).  Lane l owns the EPL consecutive samples l*EPL .. l*EPL+EPL-1 -- composite_ray's mapping -- so a lane's points4 loads are
+// 16 * EPL contiguous bytes, coalesced across the wave.  Each lane gathers its samples' logits ONCE into registers (eight corners per sample:
+// four pairs of x-neighbours, a pair adjacent in memory and requested together), then composite_ray<EPL> runs on those registers.
+// volume_lookup_kernel<HALF>: the same per-sample device function, one thread per sample, the logits alone (no compositing).
+// Every multiply-add is spelled __fmaf_rn and every product that feeds a sum or a difference goes through rounded(): this build's
+// -ffp-contract=fast would otherwise fuse them per instantiation (nrnerf_composite_ray.h), and the two kernels must give the same bits.
+#include <hip/hip_runtime.h>
+
+#include "nrnerf_volume.h"
+#include "nrnerf_composite_ray.h"
+
+namespace nrn {
+
+namespace {
+
+constexpr int VOL_WAVES = 4;            // waves (= rays in flight) per workgroup
+constexpr int VOL_MAXS = 1024;          // NRNERF_MAX_SAMPLES: EPL <= 16
+
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+
+// lerp with exact ends: f = 0 returns a, f = 1 returns b
+__device__ __forceinline__ f32x4 lerp4(const f32x4 a, const f32x4 b, const float f) {
+    f32x4 r;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) r[c] = __fmaf_rn(f, b[c], __fmaf_rn(-f, a[c], a[c]));
+    return r;
+}
+
+// vertices v and v + 1 (x-neighbours: 32 / 16 contiguous bytes), widened to fp32
+template <bool HALF>
+__device__ __forceinline__ void load_pair(const void* vol, const size_t v, f32x4& a, f32x4& b) {
+    if constexpr (HALF) {
+        const __attribute__((address_space(1))) h16x4* p = (const __attribute__((address_space(1))) h16x4*)vol + v;
+        const h16x4 ha = p[0], hb = p[1];
+        a = __builtin_convertvector(ha, f32x4);
+        b = __builtin_convertvector(hb, f32x4);
+    } else {
+        const __attribute__((address_space(1))) f32x4* p = (const __attribute__((address_space(1))) f32x4*)vol + v;
+        a = p[0];
+        b = p[1];
+    }
+}
+
+// the volume's value at (px, py, pz): include/nrnerf.h, "THE VALUE AT A POINT"
+template <bool HALF>
+__device__ __forceinline__ f32x4 volume_at(const VolumeArgs& a, const float px, const float py, const float pz) {
+    const float p[3] = {px, py, pz};
+    int i[3];
+    float f[3];
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float g = rounded(__fsub_rn(p[c], a.lo[c]) * a.scale[c]);
+        const bool in = g >= 0.0f && g <= a.top[c];          // (NaN: false)
+        ok = ok && in;
+        const float gs = in ? g : 0.0f;
+        int ic = (int)floorf(gs);
+        ic = ic < a.g[c] - 2 ? ic : a.g[c] - 2;              // 0 <= ic <= g - 2: every corner index is inside the volume
+        i[c] = ic;
+        f[c] = __fsub_rn(gs, (float)ic);
+    }
+    f32x4 r = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (ok) {
+        const size_t gx = (size_t)a.g[0], gxy = gx * (size_t)a.g[1];
+        const size_t v = (size_t)i[2] * gxy + (size_t)i[1] * gx + (size_t)i[0];
+        f32x4 c000, c100, c010, c110, c001, c101, c011, c111;
+        load_pair<HALF>(a.vol, v, c000, c100);
+        load_pair<HALF>(a.vol, v + gx, c010, c110);
+        load_pair<HALF>(a.vol, v + gxy, c001, c101);
+        load_pair<HALF>(a.vol, v + gxy + gx, c011, c111);
+        const f32x4 x00 = lerp4(c000, c100, f[0]), x10 = lerp4(c010, c110, f[0]);
+        const f32x4 x01 = lerp4(c001, c101, f[0]), x11 = lerp4(c011, c111, f[0]);
+        r = lerp4(lerp4(x00, x10, f[1]), lerp4(x01, x11, f[1]), f[2]);
+    }
+    return r;
+}
+
+// the logits of sample ic (< S) of `ray`: its point (points4, or o + d z as sample_points_kernel rounds it, z as composite_ray computes it),
+// the lookup, the removal knob
+template <bool HALF>
+__device__ __forceinline__ f32x4 sample_logits(const VolumeArgs& a, const int ray, const int ic) {
+    const int S = a.c.S;
+    float px, py, pz, rig = 0.0f;
+    if (a.points4) {
+        const f32x4 q = *(const __attribute__((address_space(1))) f32x4*)(gmem(a.points4) + ((size_t)ray * S + ic) * 4);
+        px = q[0]; py = q[1]; pz = q[2]; rig = q[3];
+    } else {
+        const __attribute__((address_space(1))) float* rp = gmem(a.c.rays) + (size_t)ray * a.c.ray_stride;
+        float z;
+        if (a.c.z) z = gmem(a.c.z)[(size_t)ray * S + ic];
+        else {
+            const float near = rp[6], far = rp[7];
+            const float t = c_lin01(ic, S);
+            if (a.c.lindisp)
+                z = __fdiv_rn(1.0f, __fadd_rn(rounded(__fdiv_rn(1.0f, near) * __fsub_rn(1.0f, t)), rounded(__fdiv_rn(1.0f, far) * t)));
+            else
+                z = __fadd_rn(rounded(near * __fsub_rn(1.0f, t)), rounded(far * t));
+        }
+        px = __fadd_rn(rp[0], rounded(rp[3] * z));
+        py = __fadd_rn(rp[1], rounded(rp[4] * z));
+        pz = __fadd_rn(rp[2], rounded(rp[5] * z));
+    }
+    f32x4 r = volume_at<HALF>(a, px, py, pz);
+    if (a.has_removal && rig >= a.removal) r[3] = rounded(r[3] * 0.0f);          // rnh:308-311 (a product: NaN stays NaN)
+    return r;
+}
+
+template <int EPL, bool HALF>
+__global__ void __launch_bounds__(VOL_WAVES * 64) volume_render_kernel(const VolumeArgs a) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int S = a.c.S;
+    const long long step = (long long)gridDim.x * VOL_WAVES;
+    for (long long rr = (long long)blockIdx.x * VOL_WAVES + wave; rr < a.c.n_rays; rr += step) {
+        const int ray = (int)rr;
+        f32x4 raw[EPL];
+#pragma unroll
+        for (int k = 0; k < EPL; ++k) {
+            const int i = lane * EPL + k;
+            raw[k] = sample_logits<HALF>(a, ray, i < S ? i : S - 1);           // (beyond S: the last sample's, as composite_ray asks for)
+            if (a.raw_out && i < S) *(__attribute__((address_space(1))) f32x4*)(gmem(a.raw_out) + ((size_t)ray * S + i) * 4) = raw[k];
+        }
+        // composite_ray asks for this lane's samples once each, in order k = 0 .. EPL-1 (its loading loop, fully unrolled): the k-th request
+        // is answered from the k-th register -- a compile-time index after unrolling, no gather is repeated and nothing is indexed dynamically
+        int next = 0;
+        float z[EPL + 1], w[EPL];
+        composite_ray<EPL>(a.c, ray, true, lane, [&](int) { return raw[next++]; }, z, w);
+    }
+}
+
+template <bool HALF>
+__global__ void __launch_bounds__(256) volume_lookup_kernel(const VolumeArgs a) {
+    const int S = a.c.S;
+    const long long total = (long long)a.c.n_rays * S, step = (long long)gridDim.x * 256;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += step) {
+        const int ray = (int)(t / S), i = (int)(t % S);
+        *(__attribute__((address_space(1))) f32x4*)(gmem(a.raw_out) + (size_t)t * 4) = sample_logits<HALF>(a, ray, i);
+    }
+}
+
+template <int EPL>
+hipError_t launch_epl(const VolumeArgs& a, int num_cus, hipStream_t stream) {
+    const long long want = ((long long)a.c.n_rays + VOL_WAVES - 1) / VOL_WAVES, cap = (long long)(num_cus > 0 ? num_cus : 256) * 16;
+    const dim3 grid((unsigned)(want < cap ? want : cap));
+    if (a.half) hipLaunchKernelGGL((volume_render_kernel<EPL, true>), grid, dim3(VOL_WAVES * 64), 0, stream, a);
+    else hipLaunchKernelGGL((volume_render_kernel<EPL, false>), grid, dim3(VOL_WAVES * 64), 0, stream, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_volume_render(const VolumeArgs& a, int num_cus, hipStream_t stream) {
+    if (a.c.S < 1 || a.c.S > VOL_MAXS) return hipErrorInvalidValue;
+    if (a.c.n_rays <= 0) return hipSuccess;
+    if (!a.c.rgb) {                         // the lookup alone
+        if (!a.raw_out) return hipErrorInvalidValue;
+        const long long want = ((long long)a.c.n_rays * a.c.S + 255) / 256, cap = (long long)(num_cus > 0 ? num_cus : 256) * 32;
+        const dim3 grid((unsigned)(want < cap ? want : cap));
+        if (a.half) hipLaunchKernelGGL(volume_lookup_kernel<true>, grid, dim3(256), 0, stream, a);
+        else hipLaunchKernelGGL(volume_lookup_kernel<false>, grid, dim3(256), 0, stream, a);
+        return hipGetLastError();
+    }
+    switch ((a.c.S + 63) / 64) {            // samples per lane, as composite_kernel's dispatch
+        case 1: return launch_epl<1>(a, num_cus, stream);
+        case 2: return launch_epl<2>(a, num_cus, stream);
+        case 3: return launch_epl<3>(a, num_cus, stream);
+        case 4: return launch_epl<4>(a, num_cus, stream);
+        case 5: case 6: return launch_epl<6>(a, num_cus, stream);
+        case 7: case 8: return launch_epl<8>(a, num_cus, stream);
+        case 9: case 10: case 11: case 12: return launch_epl<12>(a, num_cus, stream);
+        default: return launch_epl<16>(a, num_cus, stream);
+    }
+}
+
+}  // namespace nrn

@@ -3,7 +3,8 @@
 ``sample_grid`` evaluates the networks at the vertices of a box -- what NeRF-family users do with the reference's
 ``network_query_fn`` (train.py:633-649) to cut slices, extract iso-surfaces or build occupancy grids -- without an array of raw
 network outputs for the whole grid ever existing: the grid is walked in slabs of whole x-rows through ``nrnerf_grid_points`` ->
-``nrnerf_query`` -> ``nrnerf_field_from_raw``, all on the device.
+``nrnerf_query`` -> ``nrnerf_field_from_raw``, all on the device.  ``bake`` keeps the raw logits of such a grid instead, and ``render_volume``
+renders any time step from one canonical bake: the ray bender on the frame's samples, then a lookup-and-composite kernel, no network pass.
 """
 from __future__ import annotations
 
@@ -524,3 +525,259 @@ def write_ply(path, mesh) -> None:
         f.write(("\n".join(lines) + "\n").encode("ascii"))
         f.write(vrec.tobytes())
         f.write(frec.tobytes())
+
+
+# --------------------------------------------------------------------------------------------
+# baked volumes of the field (nrnerf_volume_render / nrnerf_bend_points): bake once, render every frame by lookup
+# --------------------------------------------------------------------------------------------
+_VOLUME_DTYPES = {torch.float32: _lib.VOLUME_F32, torch.float16: _lib.VOLUME_F16}
+
+
+def volume_grid_shape(resolution):
+    """``grid_shape`` for a volume that is interpolated: every axis needs two vertices, and the grid at most 2^30 of them.  Pure."""
+    g = grid_shape(resolution)
+    if min(g) < 2:
+        raise ValueError(f"a baked volume needs at least 2 vertices per axis, got {g}")
+    if g[0] * g[1] * g[2] > _lib.VOLUME_MAX_VERTICES:
+        raise ValueError(f"a baked volume has at most {_lib.VOLUME_MAX_VERTICES} vertices, got {g}")
+    return g
+
+
+def bake(render_kwargs, latent=None, min_point=None, max_point=None, resolution=128, *, fine=True, with_bending=False, dtype=torch.float32,
+         rows_per_launch=None, precision=None, checkpoint=None):
+    """The field's raw outputs on a regular grid, kept as LOGITS: ``{"raw": [Gz, Gy, Gx, 4] (r, g, b, sigma before the sigmoid / relu),
+    "min_point", "max_point"}`` -- what ``render_volume`` interpolates.  ``sample_grid``'s slab loop (``nrnerf_grid_points`` -> ``nrnerf_query``)
+    writing the first four raw channels instead of going through ``nrnerf_field_from_raw``; the result does not depend on ``rows_per_launch``.
+
+    ``with_bending=False`` (the default) bakes the CANONICAL volume, which does not depend on time: one bake serves every time step, the ray
+    bender is applied to the samples at render time.  ``with_bending=True`` bakes the observed space of ONE time step (``latent``); the
+    time-conditioned baseline always bakes per code.  ``dtype``: ``torch.float32`` or ``torch.float16`` (the float32 bake rounded once; 8 bytes
+    per vertex).  ``resolution``: an int or ``(Gx, Gy, Gz)``, each 2 .. ``MAX_SAMPLES``.  The extent defaults to the checkpoint's volume extent.
+    A view-dependent head raises ``Unsupported``: its colour is not a function of position."""
+    if dtype not in _VOLUME_DTYPES:
+        raise ValueError(f"a baked volume is float32 or float16, got {dtype}")
+    net = render_kwargs.get("network_fine") if fine and render_kwargs.get("network_fine") is not None else render_kwargs["network_fn"]
+    if bool(getattr(net, "use_viewdirs", False)):
+        raise R.Unsupported("a view-dependent head cannot be baked: its colour is not a function of position")
+    if min_point is None or max_point is None:
+        from .visualize import volume_extent_of
+        ext = volume_extent_of(checkpoint) if checkpoint is not None else None
+        if ext is None:
+            raise ValueError("bake needs min_point / max_point (or a checkpoint that carries its volume extent)")
+        min_point, max_point = ext
+    gx, gy, gz = volume_grid_shape(resolution)
+    lo, hi = grid_extent(min_point, max_point)
+    if not (hi > lo).all():
+        raise ValueError(f"a baked volume needs min < max on every axis, got {lo} .. {hi}")
+    if not with_bending:
+        net = canonical_view(net)
+    dev = next(net.parameters()).device
+    if dev.type != "cuda":
+        dev = latent.device if torch.is_tensor(latent) and latent.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+    model = R.get_model(net, None, precision=precision, device=dev)
+    dev = model.device
+    lat = None
+    if model.needs_latents:
+        if latent is None:
+            raise ValueError("this model needs a latent code")
+        lat = torch.as_tensor(latent).to(device=dev, dtype=torch.float32).reshape(1, -1).contiguous()
+    n_rows = gy * gz
+    slabs = plan_slabs(n_rows, default_rows_per_launch(gx) if rows_per_launch is None else rows_per_launch)
+    vol = torch.empty((gz, gy, gx, 4), dtype=dtype, device=dev)
+    vol_rows = vol.view(n_rows, gx, 4)
+    knobs = R._query_knobs(net)
+    lib = _lib.load()
+    fp = C.POINTER(C.c_float)
+    ch = model.coarse_output_ch
+    rows_max = max(n for _, n in slabs)
+    pts = torch.empty((rows_max, gx, 4), dtype=torch.float32, device=dev)
+    raw = torch.empty((rows_max, gx, ch), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), torch.no_grad():
+        for first, n in slabs:
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.nrnerf_grid_points(lo.ctypes.data_as(fp), hi.ctypes.data_as(fp), gx, gy, gz, first, n, pts.data_ptr(), stream),
+                       "nrnerf_grid_points")
+            try:
+                model.query(pts[:n], None if lat is None else lat.expand(n, -1), None, 0, out={"raw": raw[:n]}, **knobs)
+            except _lib.NrnerfError as e:
+                if e.status != _lib.ERR_UNSUPPORTED:
+                    raise
+                raise R.Unsupported(str(e)) from e
+            vol_rows[first:first + n].copy_(raw[:n, :, :4])
+    return {"raw": vol, "min_point": lo, "max_point": hi}
+
+
+def _volume_parts(volume):
+    """``volume`` (what ``bake`` returns) -> ``(raw [Gz, Gy, Gx, 4] contiguous on the device, lo, hi, (Gx, Gy, Gz))``."""
+    raw = volume["raw"]
+    if not torch.is_tensor(raw) or raw.device.type != "cuda":
+        raise R.Unsupported("the volume is not on a ROCm device")
+    if raw.dim() != 4 or raw.shape[-1] != 4 or raw.dtype not in _VOLUME_DTYPES:
+        raise ValueError(f"a volume is float32 or float16 [Gz, Gy, Gx, 4], got {raw.dtype} {tuple(raw.shape)}")
+    gz, gy, gx = (int(v) for v in raw.shape[:3])
+    if min(gx, gy, gz) < 2 or gx * gy * gz > _lib.VOLUME_MAX_VERTICES:
+        raise ValueError(f"a volume has 2 or more vertices per axis and at most {_lib.VOLUME_MAX_VERTICES} in all, got {(gx, gy, gz)}")
+    lo, hi = grid_extent(volume["min_point"], volume["max_point"])
+    if not (hi > lo).all():
+        raise ValueError(f"a volume needs min < max on every axis, got {lo} .. {hi}")
+    return raw.detach().contiguous(), lo, hi, (gx, gy, gz)
+
+
+def volume_render(volume, rays, *, N_samples, z_vals=None, points4=None, lindisp=False, white_bkgd=False, removal_threshold=None,
+                  composite=True, retraw=False, weights=False, alpha=False, surface=False):
+    """``nrnerf_volume_render`` on tensors: the volume's logits at the ``N_samples`` samples of every ray -- ``points4 [N, S, 4]`` (xyz, rigidity),
+    or ``o + d z`` -- and their compositing.  ``rays [N, >= 8]``; ``z_vals [N, S]`` or the coarse spacing between the rays' near and far.
+    Returns ``rgb_map / disp_map / acc_map`` (+ ``raw``, ``weights``, ``alpha``, ``surface_pts``, ``surface_rigidity``, ``median_index`` as asked
+    for); ``composite=False`` runs the lookup alone and returns ``raw``.  The sampling rule: include/nrnerf.h."""
+    vol, lo, hi, g = _volume_parts(volume)
+    dev = vol.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    if rays.dim() != 2 or rays.shape[1] < 8:
+        raise ValueError(f"rays must be [N, >= 8], got {tuple(rays.shape)}")
+    rays = rays.detach().to(**f32).contiguous()
+    N, S = int(rays.shape[0]), int(N_samples)
+    if not 1 <= S <= _lib.MAX_SAMPLES:
+        raise ValueError(f"1 <= N_samples <= {_lib.MAX_SAMPLES}, got {S}")
+    a = _lib.VolumeRenderArgs()
+    a.struct_size = C.sizeof(_lib.VolumeRenderArgs)
+    a.n_rays, a.n_samples = N, S
+    a.rays, a.ray_stride = rays.data_ptr() or None, int(rays.shape[1])
+    a.lindisp, a.white_bkgd = int(bool(lindisp)), int(bool(white_bkgd))
+    if z_vals is not None:
+        if tuple(z_vals.shape) != (N, S):
+            raise ValueError(f"z_vals must be {(N, S)}, got {tuple(z_vals.shape)}")
+        z_vals = z_vals.detach().to(**f32).contiguous()
+        a.z = z_vals.data_ptr() or None
+    if points4 is not None:
+        if tuple(points4.shape) != (N, S, 4):
+            raise ValueError(f"points4 must be {(N, S, 4)}, got {tuple(points4.shape)}")
+        points4 = points4.detach().to(**f32).contiguous()
+        a.points4 = points4.data_ptr() or None
+    elif removal_threshold is not None or surface:
+        raise ValueError("a removal threshold and the surface outputs need points4")
+    a.volume, a.volume_dtype = vol.data_ptr(), _VOLUME_DTYPES[vol.dtype]
+    a.g[:] = g
+    a.min_point[:], a.max_point[:] = lo.tolist(), hi.tolist()
+    if removal_threshold is not None:
+        a.has_removal_threshold, a.removal_threshold = 1, float(removal_threshold)
+    out = {}
+
+    def new(key, *shape, dtype=torch.float32):
+        out[key] = torch.empty(shape, dtype=dtype, device=dev)
+        return out[key].data_ptr() or None
+
+    if composite:
+        a.rgb, a.disp, a.acc = new("rgb_map", N, 3), new("disp_map", N), new("acc_map", N)
+        if weights:
+            a.weights = new("weights", N, S)
+        if alpha:
+            a.alpha = new("alpha", N, S)
+        if surface:
+            a.surface_pts, a.surface_rigidity = new("surface_pts", N, 3), new("surface_rigidity", N)
+            a.median_index = new("median_index", N, dtype=torch.int32)
+    elif weights or alpha or surface:
+        raise ValueError("weights, alpha and the surface outputs come from compositing")
+    if retraw or not composite:
+        a.raw = new("raw", N, S, 4)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().nrnerf_volume_render(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "nrnerf_volume_render")
+    return out
+
+
+def sample_rays(rays, N_samples, lindisp=False):
+    """``nrnerf_sample_depths_points`` without jitter: ``(z [N, S], points [N, S, 3])`` of the coarse spacing, ``S >= 2``."""
+    N, S = int(rays.shape[0]), int(N_samples)
+    dev = rays.device
+    z = torch.empty((N, S), dtype=torch.float32, device=dev)
+    pts = torch.empty((N, S, 3), dtype=torch.float32, device=dev)
+    if N:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().nrnerf_sample_depths_points(rays.data_ptr(), int(rays.shape[1]), None, N, S, int(bool(lindisp)), z.data_ptr(),
+                                                               pts.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                       "nrnerf_sample_depths_points")
+    return z, pts
+
+
+def render_volume(volume, rays, *, network=None, latents=None, N_samples=192, z_vals=None, lindisp=False, white_bkgd=False, surface=False,
+                  retraw=False, removal_threshold=None, precision=None):
+    """A baked volume rendered along ``rays [N, >= 8]``: ``rgb_map / disp_map / acc_map`` (+ ``raw`` under ``retraw``; ``surface_pts``,
+    ``surface_rigidity``, ``median_index`` under ``surface``), no trunk pass.
+
+    ``network`` with a ray bender and a CANONICAL bake: the samples (``N_samples`` of the coarse spacing, ``lindisp`` honoured, or ``z_vals
+    [N, S]``) are bent with ``latents`` (``[N, latent_size]``, or one code ``[latent_size]`` / ``[1, latent_size]`` for all rays) by
+    ``nrnerf_bend_points`` -- the modules' knobs (``rigidity_test_time_cutoff``, ``test_time_scaling``, and the removal threshold unless
+    ``removal_threshold`` is given) as ``query_points`` reads them -- and looked up at the bent points: any time step, motion exaggeration and
+    background stabilisation included, from one bake.  Without ``network`` (or without a bender): straight rays, no bender launch -- a bake of
+    one time step's observed space, or a static scene.  Refuses autograd inputs (``Unsupported``): a preview has no gradient."""
+    if rays.device.type != "cuda":
+        raise R.Unsupported("rays are not on a ROCm device")
+    lat_t = latents if torch.is_tensor(latents) else None
+    if torch.is_grad_enabled() and (rays.requires_grad or (lat_t is not None and lat_t.requires_grad) or volume["raw"].requires_grad
+                                    or (z_vals is not None and z_vals.requires_grad)):
+        raise R.Unsupported("autograd is enabled (rendering a baked volume has no gradient)")
+    dev = rays.device
+    rays = rays.detach().to(dtype=torch.float32).contiguous()
+    N, S = int(rays.shape[0]), int(z_vals.shape[1] if z_vals is not None else N_samples)
+    bender = R._bender_of(network) if network is not None else None
+    with torch.no_grad():
+        if z_vals is not None:
+            z = z_vals.detach().to(device=dev, dtype=torch.float32).contiguous()
+            pts = None
+        elif S >= 2:
+            z, pts = sample_rays(rays, S, lindisp)
+        else:       # one sample: the near bound
+            z, pts = (1.0 / (1.0 / rays[:, 6:7])).contiguous() if lindisp else rays[:, 6:7].contiguous(), None
+        points4 = None
+        if bender is not None or surface:
+            if pts is None:
+                pts = rays[:, None, 0:3] + rays[:, None, 3:6] * z[..., None]        # a product and a sum, each rounded, as the kernels'
+        if bender is not None:
+            if latents is None:
+                raise ValueError("a ray bender needs latents")
+            lat = torch.as_tensor(latents).detach().to(device=dev, dtype=torch.float32)
+            if lat.dim() == 1:
+                lat = lat[None]
+            if lat.dim() != 2 or lat.shape[0] not in (1, N):
+                raise ValueError(f"latents must be [N, latent_size] or one code, got {tuple(lat.shape)}")
+            if lat.shape[0] == 1:
+                lat = lat.contiguous().expand(N, -1)
+            knobs = R._query_knobs(network)
+            if removal_threshold is None:
+                removal_threshold = knobs["removal_threshold"]
+            model = R.get_model(network, None, precision=precision, device=dev)
+            try:
+                points4 = model.bend_points(pts, lat, rigidity_cutoff=knobs["rigidity_cutoff"], test_time_scaling=knobs["test_time_scaling"])
+            except _lib.NrnerfError as e:
+                if e.status != _lib.ERR_UNSUPPORTED:
+                    raise
+                raise R.Unsupported(str(e)) from e
+        elif surface:
+            points4 = torch.cat([pts, torch.zeros_like(pts[..., :1])], -1)
+        if points4 is None:
+            removal_threshold = None
+        return volume_render(volume, rays, N_samples=S, z_vals=z, points4=points4, lindisp=lindisp, white_bkgd=white_bkgd,
+                             removal_threshold=removal_threshold, retraw=retraw, surface=surface)
+
+
+def render_volume_frames(volume, render_poses, intrinsics, near, far, *, network=None, latents=None, **kwargs):
+    """``render_volume`` for every camera of ``render_poses`` (``driver.generate_rays`` per frame): ``(rgbs uint8 [F, H, W, 3], disps float32
+    [F, H, W])`` on the device, ``rgbs`` by the reference's truncating ``to8b`` (run_nerf_helpers.py:19).  ``latents``: one code per frame
+    ``[F, latent_size]``, or one code for all frames; ``kwargs``: ``render_volume``'s."""
+    from .driver import generate_rays
+    dev = volume["raw"].device
+    H, W = int(intrinsics["height"]), int(intrinsics["width"])
+    n_frames = len(render_poses)
+    rgbs = torch.empty((n_frames, H, W, 3), dtype=torch.uint8, device=dev)
+    disps = torch.empty((n_frames, H, W), dtype=torch.float32, device=dev)
+    lat = None if latents is None else torch.as_tensor(latents).detach().to(device=dev, dtype=torch.float32)
+    if lat is not None and lat.dim() == 1:
+        lat = lat[None]
+    if lat is not None and lat.shape[0] not in (1, n_frames):
+        raise ValueError(f"latents must be one code or one per frame ({n_frames}), got {tuple(lat.shape)}")
+    for i in range(n_frames):
+        rays = generate_rays(render_poses[i], intrinsics, near, far, False, dev)
+        code = None if lat is None else lat[i if lat.shape[0] > 1 else 0][None]
+        out = render_volume(volume, rays, network=network, latents=code, **kwargs)
+        rgbs[i] = (255 * out["rgb_map"].clamp(0, 1)).to(torch.uint8).view(H, W, 3)          # to8b: clip, scale, truncate
+        disps[i] = out["disp_map"].view(H, W)
+    return rgbs, disps

@@ -635,6 +635,52 @@ class Model:
                 self.note_use(dev)
         return points, residual, iterations
 
+    def bend_points(self, points: torch.Tensor, latents: torch.Tensor, *, rigidity_cutoff=None, test_time_scaling=None,
+                    flags: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+        """``nrnerf_bend_points``: the bender step of ``query`` by itself -- ``points [N, S, 3 | 4]`` with the codes ``latents [N, latent_size]``
+        (or one row, stride 0) to ``bent4 [N, S, 4]`` = (bent xyz, rigidity mask), the bits of ``query``'s ``input_pts`` / ``rigidity_mask`` on
+        this handle.  ``out``: a contiguous float32 ``[N, S, 4]`` tensor to write into."""
+        if points.dim() != 3 or points.shape[-1] not in (3, 4):
+            raise ValueError(f"points must have shape (N, S, 3) or (N, S, 4), got {tuple(points.shape)}")
+        N, S = int(points.shape[0]), int(points.shape[1])
+        if not 1 <= S <= _lib.MAX_SAMPLES:
+            raise ValueError(f"1 <= samples per row <= {_lib.MAX_SAMPLES}, got {S}")
+        dev = self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        points = points.to(**f32).contiguous()
+        a = _lib.BendPointsArgs()
+        a.struct_size = C.sizeof(_lib.BendPointsArgs)
+        a.n_rows, a.n_samples = N, S
+        a.points, a.point_stride = points.data_ptr(), int(points.shape[-1])
+        if latents is None:
+            raise ValueError("ray_bending_latents are required")
+        if latents.dim() != 2 or latents.shape[0] != N or latents.shape[1] != self.latent_size:
+            raise ValueError(f"ray_bending_latents must have shape ({N}, {self.latent_size}), got {tuple(latents.shape)}")
+        if latents.stride(0) == 0 and latents.stride(1) == 1 and latents.dtype == torch.float32 and latents.device == dev:
+            a.latents, a.latent_stride = latents.data_ptr(), 0           # one code for the call
+        else:
+            latents = latents.to(**f32).contiguous()
+            a.latents, a.latent_stride = latents.data_ptr(), latents.shape[1]
+        a.flags = (_lib.render_flags_from_env() if flags is None else int(flags)) & _lib.QUERY_FLAGS
+        if rigidity_cutoff is not None:
+            a.has_rigidity_cutoff, a.rigidity_cutoff = 1, float(rigidity_cutoff)
+        if test_time_scaling is not None:
+            a.has_test_time_scaling, a.test_time_scaling = 1, float(test_time_scaling)
+        if out is None:
+            out = torch.empty((N, S, 4), **f32)
+        elif tuple(out.shape) != (N, S, 4) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous float32 tensor of shape {(N, S, 4)} on {dev}")
+        a.bent4 = out.data_ptr() or None
+        nbytes = self.lib.nrnerf_bend_points_workspace_bytes(self.handle)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            ws = self._workspace(nbytes + 256, stream)
+            a.workspace, a.workspace_bytes = (ws.data_ptr() + 255) // 256 * 256, nbytes
+            _lib.check(self.lib.nrnerf_bend_points(self.handle, C.byref(a), C.c_void_p(stream)), "nrnerf_bend_points")
+            if N > 0:
+                self.note_use(dev)
+        return out
+
     def note_use(self, dev=None):
         """Kernels reading this handle's weights were just queued on the current stream: remember an event there, so that
         a later weight refresh issued from ANOTHER stream can order itself after them (update_from_device).  The
