@@ -1083,6 +1083,71 @@ typedef struct nrnerf_bend_points_args {
 size_t nrnerf_bend_points_workspace_bytes(const nrnerf_model* model);
 int nrnerf_bend_points(const nrnerf_model* model, const nrnerf_bend_points_args* args, void* hip_stream);
 
+/* ---- ABI 10 (additions): baked warps -- the ray bender of a time step as a coarse grid, a frame rendered with no network.
+ *
+ * The deformation is a much smoother function of position than the radiance field, so a coarse grid per time step carries it: one canonical
+ * volume (above) plus one small offset grid per time step is a whole sequence, rendered by ONE kernel per frame -- sample, look the offset up,
+ * bend, look the canonical field up, composite -- with every test-time knob of the bender applied at render time (csrc/nrnerf_warp.h,
+ * DESIGN.md section 3.14).
+ *
+ * THE WARP.  A second grid by the rule of nrnerf_grid_points with its own box and resolution, row-major [Gz, Gy, Gx, 4] = (unmasked offset x,
+ * y, z, rigidity mask) -- nrnerf_query's unmasked_offsets and rigidity_mask at the vertices, baked with all knobs off; a bender without a
+ * rigidity network stores mask 1 -- as float32 or IEEE half, the base aligned to one vertex, at most 2^30 vertices.
+ * THE VALUE OF SAMPLE i OF RAY n, all in fp32, every operation rounded once, no contraction into fma beyond what is named:
+ *     p = o + d z            the product rounded before the sum, as nrnerf_sample_depths_points rounds; z = the caller's depths or the coarse
+ *                            spacing between the ray's near and far (`lindisp` honoured), as in nrnerf_volume_render
+ *     (u, m) = the warp at p by THE VALUE AT A POINT above: the same s_c, g_c, i_c, f_c, the same lerp, half widened first;
+ *              a p outside the warp's box, or NaN, gives u = 0, m = 0 -- the sample is not bent
+ *     has_rigidity_cutoff and m <= rigidity_cutoff:  m = 0                      (rnh:563-564)
+ *     off_c = m * u_c;    has_test_time_scaling:  off_c = off_c * test_time_scaling      (rnh:567-569)
+ *     bent_c = p_c + off_c
+ *     raw = the canonical volume at bent by THE VALUE AT A POINT (outside its box: EMPTY, raw = 0)
+ *     has_removal_threshold and m >= removal_threshold:  the sigma logit is multiplied by 0      (rnh:308-311)
+ * then the compositing of nrnerf_volume_render, unedited; the surface outputs are its reduction over (bent, m).  points4 [N, S, 4] = (bent,
+ * m) is what nrnerf_bend_points would hand to nrnerf_volume_render: that call on points4 and the same z returns this call's bits.  With rgb,
+ * disp and acc all NULL nothing is composited: raw and / or points4 alone are written (the lookup by itself).  One kernel, no workspace, no
+ * atomics, no device counter: the same bits on every run.  Device pointers only, asynchronous on the stream, allocates nothing; runs on the
+ * device that owns rgb (raw, else points4, when nothing is composited).
+ * Checks, in this order: NRNERF_ERR_INVALID for a NULL record or a wrong struct_size; n_rays < 0, n_samples outside 1 .. NRNERF_MAX_SAMPLES,
+ * ray_stride < 8; the volume's g < 2, max_c not > min_c (NaN included), unknown volume_dtype; the same three of the warp.
+ * NRNERF_ERR_UNSUPPORTED for more than 2^30 vertices in either grid or 2^31 or more samples.  Then n_rays == 0 answers NRNERF_OK without a
+ * launch.  Then NRNERF_ERR_INVALID for a NULL rays / volume / warp; rgb, disp, acc neither all given nor all NULL; nothing to write (no maps,
+ * no raw and no points4); weights / alpha / a surface output without the maps; and -- the first HIP calls -- memory that is not device memory
+ * of one device (the warp included). */
+typedef struct nrnerf_warped_volume_render_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_warped_volume_render_args) */
+    int32_t n_rays, n_samples;  /* N >= 0, 1 <= S <= NRNERF_MAX_SAMPLES */
+    const float* rays;          /* [N, ray_stride]: o (0..2), d (3..5), near, far (6, 7) */
+    int32_t ray_stride;         /* >= 8 */
+    int32_t lindisp;            /* the coarse spacing linear in inverse depth; read when z is NULL */
+    const float* z;             /* [N, S] sample depths, or NULL: the coarse spacing */
+    const void* volume;         /* [gz, gy, gx, 4] canonical logits, float32 or half */
+    int32_t volume_dtype;       /* NRNERF_VOLUME_F32 / NRNERF_VOLUME_F16 */
+    int32_t g[3];               /* gx, gy, gz, each >= 2 */
+    float min_point[3];         /* the volume's box, as in nrnerf_grid_points; max_c > min_c */
+    float max_point[3];
+    const void* warp;           /* [wgz, wgy, wgx, 4] (unmasked offset xyz, rigidity mask), float32 or half */
+    int32_t warp_dtype;         /* NRNERF_VOLUME_F32 / NRNERF_VOLUME_F16 */
+    int32_t warp_g[3];          /* gx, gy, gz of the warp, each >= 2 */
+    float warp_min_point[3];    /* the warp's own box; max_c > min_c */
+    float warp_max_point[3];
+    int32_t has_rigidity_cutoff;    float rigidity_cutoff;      /* the knobs of nrnerf_render_args, applied here */
+    int32_t has_test_time_scaling;  float test_time_scaling;
+    int32_t white_bkgd;
+    int32_t has_removal_threshold; float removal_threshold;
+    float* rgb;                 /* out [N, 3] */
+    float* disp;                /* out [N] */
+    float* acc;                 /* out [N] */
+    float* raw;                 /* out [N, S, 4] the sampled logits (after the removal knob), or NULL */
+    float* weights;             /* out [N, S] or NULL */
+    float* alpha;               /* out [N, S] or NULL */
+    float* surface_pts;         /* out [N, 3] or NULL */
+    float* surface_rigidity;    /* out [N] or NULL */
+    int32_t* median_index;      /* out [N] or NULL */
+    float* points4;             /* out [N, S, 4] (bent xyz, rigidity after the cutoff), 16-byte aligned, or NULL */
+} nrnerf_warped_volume_render_args;
+int nrnerf_warped_volume_render(const nrnerf_warped_volume_render_args* args, void* hip_stream);
+
 /* Host-only packing (no device needed): writes the MFMA-fragment weight stream + unit table + bias
  * table of one pass exactly as nrnerf_model_create uploads them.  which: 0 = coarse, 1 = fine, 2 = fine without the
  * bender layers, 3 = bender + rigidity layers alone (2, 3: the split-bender path; need a bender and not the exact view directions),

@@ -369,6 +369,24 @@ VOLUME_F32, VOLUME_F16 = 0, 1               # NRNERF_VOLUME_F32 / NRNERF_VOLUME_
 VOLUME_MAX_VERTICES = 1 << 30
 
 
+class WarpedVolumeRenderArgs(C.Structure):
+    """nrnerf_warped_volume_render_args (ABI 10 additions): the samples of the rays bent by a baked offset grid (knobs applied here), the
+    canonical volume's logits at the bent points, composited -- one kernel, no network."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_rays", C.c_int32), ("n_samples", C.c_int32),
+                ("rays", C.c_void_p), ("ray_stride", C.c_int32), ("lindisp", C.c_int32), ("z", C.c_void_p),
+                ("volume", C.c_void_p), ("volume_dtype", C.c_int32), ("g", C.c_int32 * 3),
+                ("min_point", C.c_float * 3), ("max_point", C.c_float * 3),
+                ("warp", C.c_void_p), ("warp_dtype", C.c_int32), ("warp_g", C.c_int32 * 3),
+                ("warp_min_point", C.c_float * 3), ("warp_max_point", C.c_float * 3),
+                ("has_rigidity_cutoff", C.c_int32), ("rigidity_cutoff", C.c_float),
+                ("has_test_time_scaling", C.c_int32), ("test_time_scaling", C.c_float),
+                ("white_bkgd", C.c_int32), ("has_removal_threshold", C.c_int32), ("removal_threshold", C.c_float),
+                ("rgb", C.c_void_p), ("disp", C.c_void_p), ("acc", C.c_void_p),
+                ("raw", C.c_void_p), ("weights", C.c_void_p), ("alpha", C.c_void_p),
+                ("surface_pts", C.c_void_p), ("surface_rigidity", C.c_void_p), ("median_index", C.c_void_p),
+                ("points4", C.c_void_p)]
+
+
 class BendPointsArgs(C.Structure):
     """nrnerf_bend_points_args (ABI 10 additions): the bender step of nrnerf_query by itself, points -> bent4 (bent xyz, rigidity)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_rows", C.c_int32), ("n_samples", C.c_int32),
@@ -430,6 +448,7 @@ EXPORTS = {
     "nrnerf_bender_inverse_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "nrnerf_bender_inverse": (C.c_int, [C.c_void_p, C.POINTER(BenderInverseArgs), C.c_void_p]),
     "nrnerf_volume_render": (C.c_int, [C.POINTER(VolumeRenderArgs), C.c_void_p]),
+    "nrnerf_warped_volume_render": (C.c_int, [C.POINTER(WarpedVolumeRenderArgs), C.c_void_p]),
     "nrnerf_bend_points_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "nrnerf_bend_points": (C.c_int, [C.c_void_p, C.POINTER(BendPointsArgs), C.c_void_p]),
     "nrnerf_generate_rays": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),

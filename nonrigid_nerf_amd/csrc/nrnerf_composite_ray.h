@@ -167,6 +167,8 @@ __device__ __forceinline__ void composite_ray(const CompositeArgs& a, const int 
     }
 
     phase_fence();
+    // (warped_render_kernel, nrnerf_warp.hip, keeps its bent points in registers and carries a copy of this block on the weights returned
+    //  in w: a change here is a change there; tests/test_warp.py compares the two bit for bit)
     // ---- surface reduction: index of the sample whose accumulated visibility is closest to 0.5 (first one on ties),
     //      and the bent point / rigidity there (free_viewpoint_rendering.py:621-648 does this on the host from the
     //      full per-sample tensors: ~15 KB/ray of D2H traffic instead of 20 B/ray)

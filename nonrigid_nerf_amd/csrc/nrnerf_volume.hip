@@ -7,12 +7,14 @@
 // 16 * EPL contiguous bytes, coalesced across the wave.  Each lane gathers its samples' logits ONCE into registers (eight corners per sample:
 // four pairs of x-neighbours, a pair adjacent in memory and requested together), then composite_ray<EPL> runs on those registers.
 // volume_lookup_kernel<HALF>: the same per-sample device function, one thread per sample, the logits alone (no compositing).
+// The lookup itself (lerp4 / load_pair / volume_at) lives in nrnerf_volume_lookup.h, shared with nrnerf_warp.hip.
 // Every multiply-add is spelled __fmaf_rn and every product that feeds a sum or a difference goes through rounded(): this build's
 // -ffp-contract=fast would otherwise fuse them per instantiation (nrnerf_composite_ray.h), and the two kernels must give the same bits.
 #include <hip/hip_runtime.h>
 
 #include "nrnerf_volume.h"
 #include "nrnerf_composite_ray.h"
+#include "nrnerf_volume_lookup.h"
 
 namespace nrn {
 
@@ -20,65 +22,6 @@ namespace {
 
 constexpr int VOL_WAVES = 4;            // waves (= rays in flight) per workgroup
 constexpr int VOL_MAXS = 1024;          // NRNERF_MAX_SAMPLES: EPL <= 16
-
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-
-// lerp with exact ends: f = 0 returns a, f = 1 returns b
-__device__ __forceinline__ f32x4 lerp4(const f32x4 a, const f32x4 b, const float f) {
-    f32x4 r;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) r[c] = __fmaf_rn(f, b[c], __fmaf_rn(-f, a[c], a[c]));
-    return r;
-}
-
-// vertices v and v + 1 (x-neighbours: 32 / 16 contiguous bytes), widened to fp32
-template <bool HALF>
-__device__ __forceinline__ void load_pair(const void* vol, const size_t v, f32x4& a, f32x4& b) {
-    if constexpr (HALF) {
-        const __attribute__((address_space(1))) h16x4* p = (const __attribute__((address_space(1))) h16x4*)vol + v;
-        const h16x4 ha = p[0], hb = p[1];
-        a = __builtin_convertvector(ha, f32x4);
-        b = __builtin_convertvector(hb, f32x4);
-    } else {
-        const __attribute__((address_space(1))) f32x4* p = (const __attribute__((address_space(1))) f32x4*)vol + v;
-        a = p[0];
-        b = p[1];
-    }
-}
-
-// the volume's value at (px, py, pz): include/nrnerf.h, "THE VALUE AT A POINT"
-template <bool HALF>
-__device__ __forceinline__ f32x4 volume_at(const VolumeArgs& a, const float px, const float py, const float pz) {
-    const float p[3] = {px, py, pz};
-    int i[3];
-    float f[3];
-    bool ok = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float g = rounded(__fsub_rn(p[c], a.lo[c]) * a.scale[c]);
-        const bool in = g >= 0.0f && g <= a.top[c];          // (NaN: false)
-        ok = ok && in;
-        const float gs = in ? g : 0.0f;
-        int ic = (int)floorf(gs);
-        ic = ic < a.g[c] - 2 ? ic : a.g[c] - 2;              // 0 <= ic <= g - 2: every corner index is inside the volume
-        i[c] = ic;
-        f[c] = __fsub_rn(gs, (float)ic);
-    }
-    f32x4 r = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (ok) {
-        const size_t gx = (size_t)a.g[0], gxy = gx * (size_t)a.g[1];
-        const size_t v = (size_t)i[2] * gxy + (size_t)i[1] * gx + (size_t)i[0];
-        f32x4 c000, c100, c010, c110, c001, c101, c011, c111;
-        load_pair<HALF>(a.vol, v, c000, c100);
-        load_pair<HALF>(a.vol, v + gx, c010, c110);
-        load_pair<HALF>(a.vol, v + gxy, c001, c101);
-        load_pair<HALF>(a.vol, v + gxy + gx, c011, c111);
-        const f32x4 x00 = lerp4(c000, c100, f[0]), x10 = lerp4(c010, c110, f[0]);
-        const f32x4 x01 = lerp4(c001, c101, f[0]), x11 = lerp4(c011, c111, f[0]);
-        r = lerp4(lerp4(x00, x10, f[1]), lerp4(x01, x11, f[1]), f[2]);
-    }
-    return r;
-}
 
 // the logits of sample ic (< S) of `ray`: its point (points4, or o + d z as sample_points_kernel rounds it, z as composite_ray computes it),
 // the lookup, the removal knob

@@ -1,0 +1,216 @@
+// nrnerf_warp.hip -- a baked scene rendered with no network: per sample the ray bender's (offset, rigidity mask) from a coarse grid baked per
+// time step, the bend with its test-time knobs, the canonical volume's logits at the bent point, then the alpha compositing of
+// nrnerf_composite_ray.h -- ONE kernel, nothing per sample goes through memory.  The value rule is stated in include/nrnerf.h ("baked warps")
+// and, in float64, in tests/warp_reference.py; layout, resources and measurements: DESIGN.md section 3.14.
+//
+// warped_render_kernel<EPL, VHALF, WHALF>: volume_render_kernel's mapping (nrnerf_volume.hip) -- one wave per ray at a time, rays handed out by
+// a grid-stride loop (no atomics, no device counter: the same bits on every run), lane l owns the EPL consecutive samples l*EPL .. l*EPL+EPL-1.
+// The two gathers of a sample depend on each other, so a lane works on GROUP samples at a time (all EPL up to 4; 3 of 6; 2 of 8 and 12; 1 of
+// 16): the warp corners of the whole group are requested before the first of them is interpolated, every bent point's canonical corners are
+// requested as soon as it is known, and the canonical interpolations start when all of the group's requests are out.  The corners of a group
+// are GROUP * 64 registers in float32: beyond EPL = 4 the groups are sized so that, next to raw[EPL], every instantiation stays within 256
+// VGPRs and parks nothing in AGPRs.  An empty sample requests nothing.  composite_ray<EPL> then runs on the registers.
+// The surface outputs: composite_ray's reduction reads the bent points from memory, where this kernel has none; it runs here on the weights
+// composite_ray returns (the same operations in the same order), and lane 0 bends the one sample it picks again.
+// warped_lookup_kernel<VHALF, WHALF>: the same per-sample rule, one thread per sample, no compositing.
+// No multiply-add is fused that the rule does not name: every product that feeds a sum goes through rounded() (nrnerf_volume_lookup.h).
+#include <hip/hip_runtime.h>
+
+#include "nrnerf_warp.h"
+#include "nrnerf_composite_ray.h"
+#include "nrnerf_volume_lookup.h"
+
+namespace nrn {
+
+namespace {
+
+constexpr int WARP_WAVES = 4;           // waves (= rays in flight) per workgroup
+constexpr int WARP_MAXS = 1024;         // NRNERF_MAX_SAMPLES: EPL <= 16
+
+// depth of sample ic (< S) of the ray at rp, as composite_ray computes it
+__device__ __forceinline__ float sample_depth(const WarpArgs& a, const __attribute__((address_space(1))) float* rp, const int ray, const int ic) {
+    const int S = a.c.S;
+    if (a.c.z) return gmem(a.c.z)[(size_t)ray * S + ic];
+    const float near = rp[6], far = rp[7];
+    const float t = c_lin01(ic, S);
+    if (a.c.lindisp) return __fdiv_rn(1.0f, __fadd_rn(rounded(__fdiv_rn(1.0f, near) * __fsub_rn(1.0f, t)), rounded(__fdiv_rn(1.0f, far) * t)));
+    return __fadd_rn(rounded(near * __fsub_rn(1.0f, t)), rounded(far * t));
+}
+
+// p = o + d z, the product rounded before the sum (sample_points_kernel)
+__device__ __forceinline__ void sample_point(const __attribute__((address_space(1))) float* rp, const float z, float (&p)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c] = __fadd_rn(rp[c], rounded(rp[3 + c] * z));
+}
+
+// (u, m) at p -> (bent xyz, m after the cutoff): rnh:563-570
+__device__ __forceinline__ f32x4 bend(const WarpArgs& a, const float (&p)[3], const f32x4 um) {
+    float m = um[3];
+    if (a.has_cutoff && m <= a.cutoff) m = 0.0f;
+    f32x4 b;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float off = rounded(m * um[c]);
+        if (a.has_scaling) off = rounded(off * a.scaling);
+        b[c] = __fadd_rn(p[c], off);
+    }
+    b[3] = m;
+    return b;
+}
+
+// the removal knob on a sample's logits (a product: NaN stays NaN)
+__device__ __forceinline__ f32x4 removed(const WarpArgs& a, f32x4 r, const float m) {
+    if (a.has_removal && m >= a.removal) r[3] = rounded(r[3] * 0.0f);
+    return r;
+}
+
+// sample ic of `ray` in one go: (bent xyz, m)
+template <bool WHALF>
+__device__ __forceinline__ f32x4 sample_bent(const WarpArgs& a, const int ray, const int ic) {
+    const __attribute__((address_space(1))) float* rp = gmem(a.c.rays) + (size_t)ray * a.c.ray_stride;
+    float p[3];
+    sample_point(rp, sample_depth(a, rp, ray, ic), p);
+    return bend(a, p, volume_at<WHALF>(a.warp, p[0], p[1], p[2]));
+}
+
+template <int EPL, bool VHALF, bool WHALF>
+__global__ void __launch_bounds__(WARP_WAVES * 64) warped_render_kernel(const WarpArgs a) {
+    constexpr int GROUP = EPL <= 4 ? EPL : (EPL == 6 ? 3 : (EPL == 16 ? 1 : 2));
+    static_assert(EPL % GROUP == 0, "whole groups");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int S = a.c.S;
+    const long long step = (long long)gridDim.x * WARP_WAVES;
+    for (long long rr = (long long)blockIdx.x * WARP_WAVES + wave; rr < a.c.n_rays; rr += step) {
+        const int ray = (int)rr;
+        const __attribute__((address_space(1))) float* rp = gmem(a.c.rays) + (size_t)ray * a.c.ray_stride;
+        f32x4 raw[EPL];
+#pragma unroll
+        for (int g0 = 0; g0 < EPL; g0 += GROUP) {
+            float p[GROUP][3];
+            GridFetch<WHALF> tw[GROUP];
+            GridFetch<VHALF> tv[GROUP];
+            f32x4 b[GROUP];
+#pragma unroll
+            for (int k = 0; k < GROUP; ++k) {
+                const int i = lane * EPL + g0 + k;
+                sample_point(rp, sample_depth(a, rp, ray, i < S ? i : S - 1), p[k]);        // (beyond S: the last sample's, as composite_ray asks for)
+                grid_fetch<WHALF>(a.warp, p[k][0], p[k][1], p[k][2], tw[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < GROUP; ++k) {
+                b[k] = bend(a, p[k], grid_value<WHALF>(tw[k]));
+                grid_fetch<VHALF>(a.vol, b[k][0], b[k][1], b[k][2], tv[k]);
+            }
+#pragma unroll
+            for (int k = 0; k < GROUP; ++k) {
+                const int i = lane * EPL + g0 + k;
+                raw[g0 + k] = removed(a, grid_value<VHALF>(tv[k]), b[k][3]);
+                if (i < S) {
+                    if (a.raw_out) *(__attribute__((address_space(1))) f32x4*)(gmem(a.raw_out) + ((size_t)ray * S + i) * 4) = raw[g0 + k];
+                    if (a.points4_out) *(__attribute__((address_space(1))) f32x4*)(gmem(a.points4_out) + ((size_t)ray * S + i) * 4) = b[k];
+                }
+            }
+        }
+        // composite_ray asks for this lane's samples once each, in order k = 0 .. EPL-1 (its loading loop, fully unrolled): the k-th request
+        // is answered from the k-th register, as in volume_render_kernel
+        int next = 0;
+        float z[EPL + 1], w[EPL];
+        composite_ray<EPL>(a.c, ray, true, lane, [&](int) { return raw[next++]; }, z, w);
+
+        // ---- the surface reduction of composite_ray (its last block, on the weights it returned): index of the sample whose accumulated
+        //      visibility is closest to 0.5, first one on ties; the bent point and the mask there
+        if (a.surf_pts || a.surf_rig || a.med_idx) {
+            float carry = 0.f, base = 0.f;
+            for (int l = 0; l < 64; ++l) {
+                float e = carry;
+#pragma unroll
+                for (int k = 0; k < EPL; ++k) e = __fadd_rn(e, w[k]);
+                if (lane == l) base = carry;
+                carry = __shfl(e, l);
+            }
+            float best = 3.0e38f, run_c = base;
+            int bidx = (lane * EPL < S) ? lane * EPL : S - 1;
+#pragma unroll
+            for (int k = 0; k < EPL; ++k) {
+                const int i = lane * EPL + k;
+                run_c = __fadd_rn(run_c, w[k]);
+                const float dist = fabsf(__fsub_rn(run_c, 0.5f));
+                if (i < S && dist < best) { best = dist; bidx = i; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ob = __shfl_xor(best, o);
+                const int oi = __shfl_xor(bidx, o);
+                if (ob < best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+            }
+            if (lane == 0) {
+                bidx = bidx < 0 ? 0 : (bidx > S - 1 ? S - 1 : bidx);
+                const f32x4 s = sample_bent<WHALF>(a, ray, bidx);
+                if (a.surf_pts) { gmem(a.surf_pts)[(size_t)ray * 3] = s[0]; gmem(a.surf_pts)[(size_t)ray * 3 + 1] = s[1]; gmem(a.surf_pts)[(size_t)ray * 3 + 2] = s[2]; }
+                if (a.surf_rig) gmem(a.surf_rig)[ray] = s[3];
+                if (a.med_idx) gmem(a.med_idx)[ray] = bidx;
+            }
+        }
+    }
+}
+
+template <bool VHALF, bool WHALF>
+__global__ void __launch_bounds__(256) warped_lookup_kernel(const WarpArgs a) {
+    const int S = a.c.S;
+    const long long total = (long long)a.c.n_rays * S, step = (long long)gridDim.x * 256;
+    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += step) {
+        const int ray = (int)(t / S), i = (int)(t % S);
+        const f32x4 b = sample_bent<WHALF>(a, ray, i);
+        if (a.points4_out) *(__attribute__((address_space(1))) f32x4*)(gmem(a.points4_out) + (size_t)t * 4) = b;
+        if (a.raw_out)
+            *(__attribute__((address_space(1))) f32x4*)(gmem(a.raw_out) + (size_t)t * 4) = removed(a, volume_at<VHALF>(a.vol, b[0], b[1], b[2]), b[3]);
+    }
+}
+
+template <class KERNEL>
+hipError_t launch(KERNEL kernel, const WarpArgs& a, const dim3 grid, const dim3 block, hipStream_t stream) {
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+template <int EPL>
+hipError_t launch_epl(const WarpArgs& a, int num_cus, hipStream_t stream) {
+    const long long want = ((long long)a.c.n_rays + WARP_WAVES - 1) / WARP_WAVES, cap = (long long)(num_cus > 0 ? num_cus : 256) * 16;
+    const dim3 grid((unsigned)(want < cap ? want : cap)), block(WARP_WAVES * 64);
+    switch ((a.vol.half ? 2 : 0) | (a.warp.half ? 1 : 0)) {
+        case 0: return launch(warped_render_kernel<EPL, false, false>, a, grid, block, stream);
+        case 1: return launch(warped_render_kernel<EPL, false, true>, a, grid, block, stream);
+        case 2: return launch(warped_render_kernel<EPL, true, false>, a, grid, block, stream);
+        default: return launch(warped_render_kernel<EPL, true, true>, a, grid, block, stream);
+    }
+}
+
+}  // namespace
+
+hipError_t launch_warped_volume_render(const WarpArgs& a, int num_cus, hipStream_t stream) {
+    if (a.c.S < 1 || a.c.S > WARP_MAXS) return hipErrorInvalidValue;
+    if (a.c.n_rays <= 0) return hipSuccess;
+    if (!a.c.rgb) {                         // the lookup alone
+        if (!a.raw_out && !a.points4_out) return hipErrorInvalidValue;
+        const long long want = ((long long)a.c.n_rays * a.c.S + 255) / 256, cap = (long long)(num_cus > 0 ? num_cus : 256) * 32;
+        const dim3 grid((unsigned)(want < cap ? want : cap)), block(256);
+        switch ((a.vol.half ? 2 : 0) | (a.warp.half ? 1 : 0)) {
+            case 0: return launch(warped_lookup_kernel<false, false>, a, grid, block, stream);
+            case 1: return launch(warped_lookup_kernel<false, true>, a, grid, block, stream);
+            case 2: return launch(warped_lookup_kernel<true, false>, a, grid, block, stream);
+            default: return launch(warped_lookup_kernel<true, true>, a, grid, block, stream);
+        }
+    }
+    switch ((a.c.S + 63) / 64) {            // samples per lane, as composite_kernel's dispatch
+        case 1: return launch_epl<1>(a, num_cus, stream);
+        case 2: return launch_epl<2>(a, num_cus, stream);
+        case 3: return launch_epl<3>(a, num_cus, stream);
+        case 4: return launch_epl<4>(a, num_cus, stream);
+        case 5: case 6: return launch_epl<6>(a, num_cus, stream);
+        case 7: case 8: return launch_epl<8>(a, num_cus, stream);
+        case 9: case 10: case 11: case 12: return launch_epl<12>(a, num_cus, stream);
+        default: return launch_epl<16>(a, num_cus, stream);
+    }
+}
+
+}  // namespace nrn

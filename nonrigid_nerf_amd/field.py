@@ -5,6 +5,8 @@
 network outputs for the whole grid ever existing: the grid is walked in slabs of whole x-rows through ``nrnerf_grid_points`` ->
 ``nrnerf_query`` -> ``nrnerf_field_from_raw``, all on the device.  ``bake`` keeps the raw logits of such a grid instead, and ``render_volume``
 renders any time step from one canonical bake: the ray bender on the frame's samples, then a lookup-and-composite kernel, no network pass.
+``bake_warp`` bakes the ray bender of a time step into a coarse offset grid as well, and ``render_baked`` renders a frame from the two bakes
+alone: one kernel, no network, no model handle.
 """
 from __future__ import annotations
 
@@ -778,6 +780,215 @@ def render_volume_frames(volume, render_poses, intrinsics, near, far, *, network
         rays = generate_rays(render_poses[i], intrinsics, near, far, False, dev)
         code = None if lat is None else lat[i if lat.shape[0] > 1 else 0][None]
         out = render_volume(volume, rays, network=network, latents=code, **kwargs)
+        rgbs[i] = (255 * out["rgb_map"].clamp(0, 1)).to(torch.uint8).view(H, W, 3)          # to8b: clip, scale, truncate
+        disps[i] = out["disp_map"].view(H, W)
+    return rgbs, disps
+
+
+# --------------------------------------------------------------------------------------------
+# baked warps (nrnerf_warped_volume_render): the ray bender of a time step as a coarse offset grid; a frame is one kernel
+# --------------------------------------------------------------------------------------------
+def bake_warp(render_kwargs_or_network, latent, min_point=None, max_point=None, resolution=32, *, fine=True, dtype=torch.float32,
+              rows_per_launch=None, precision=None, checkpoint=None):
+    """The ray bender of ONE time step (``latent``) on a regular grid: ``{"warp": [Gz, Gy, Gx, 4] = (unmasked offset x, y, z, rigidity mask),
+    "min_point", "max_point"}`` -- what ``render_baked`` interpolates next to a canonical ``bake``.  ``bake``'s slab loop (``nrnerf_grid_points``
+    -> ``nrnerf_query``) keeping the query's ``unmasked_offsets`` and ``rigidity_mask`` at the vertices; the result does not depend on
+    ``rows_per_launch``.  ALL THREE test-time knobs are off in the bake whatever the modules carry (the modules are not touched):
+    ``rigidity_test_time_cutoff``, ``test_time_scaling`` and the removal threshold are applied at render time.  The layout's mask of a bender
+    without rigidity network is 1; this library packs no such bender.  ``render_kwargs_or_network``: the dictionary ``load_checkpoint`` /
+    ``create_nerf`` returns (``fine`` picks ``network_fine`` when there is one) or a network module.  ``dtype``: ``torch.float32`` or
+    ``torch.float16`` (the float32 bake rounded once).  ``resolution``: an int or ``(Gx, Gy, Gz)``, each 2 .. ``MAX_SAMPLES``.  The extent
+    defaults to the checkpoint's volume extent.  No ray bender (the time-conditioned baseline included) raises ``Unsupported``."""
+    if dtype not in _VOLUME_DTYPES:
+        raise ValueError(f"a baked warp is float32 or float16, got {dtype}")
+    if isinstance(render_kwargs_or_network, dict):
+        kw = render_kwargs_or_network
+        net = kw.get("network_fine") if fine and kw.get("network_fine") is not None else kw["network_fn"]
+    else:
+        net = render_kwargs_or_network
+    if R._bender_of(net) is None:
+        raise R.Unsupported("a warp is baked from a ray bender: this network has none")
+    if min_point is None or max_point is None:
+        from .visualize import volume_extent_of
+        ext = volume_extent_of(checkpoint) if checkpoint is not None else None
+        if ext is None:
+            raise ValueError("bake_warp needs min_point / max_point (or a checkpoint that carries its volume extent)")
+        min_point, max_point = ext
+    gx, gy, gz = volume_grid_shape(resolution)
+    lo, hi = grid_extent(min_point, max_point)
+    if not (hi > lo).all():
+        raise ValueError(f"a baked warp needs min < max on every axis, got {lo} .. {hi}")
+    if latent is None:
+        raise ValueError("a ray bender needs a latent code")
+    dev = next(net.parameters()).device
+    if dev.type != "cuda":
+        dev = latent.device if torch.is_tensor(latent) and latent.device.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+    model = R.get_model(net, None, precision=precision, device=dev)
+    if not model.has_bender:
+        raise R.Unsupported("a warp is baked from a ray bender: this handle has none")
+    dev = model.device
+    lat = torch.as_tensor(latent).detach().to(device=dev, dtype=torch.float32).reshape(1, -1).contiguous()
+    n_rows = gy * gz
+    slabs = plan_slabs(n_rows, default_rows_per_launch(gx) if rows_per_launch is None else rows_per_launch)
+    warp = torch.empty((gz, gy, gx, 4), dtype=dtype, device=dev)
+    warp_rows = warp.view(n_rows, gx, 4)
+    lib = _lib.load()
+    fp = C.POINTER(C.c_float)
+    rows_max = max(n for _, n in slabs)
+    pts = torch.empty((rows_max, gx, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), torch.no_grad():
+        for first, n in slabs:
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(lib.nrnerf_grid_points(lo.ctypes.data_as(fp), hi.ctypes.data_as(fp), gx, gy, gz, first, n, pts.data_ptr(), stream),
+                       "nrnerf_grid_points")
+            try:
+                _, det = model.query(pts[:n], lat.expand(n, -1), None, 0, detailed_output=True)        # (no knob is passed: all off)
+            except _lib.NrnerfError as e:
+                if e.status != _lib.ERR_UNSUPPORTED:
+                    raise
+                raise R.Unsupported(str(e)) from e
+            warp_rows[first:first + n, :, :3].copy_(det["unmasked_offsets"])
+            warp_rows[first:first + n, :, 3:].copy_(det["rigidity_mask"])
+    return {"warp": warp, "min_point": lo, "max_point": hi}
+
+
+def bake_warps(render_kwargs_or_network, latents, min_point=None, max_point=None, resolution=32, **kwargs):
+    """``bake_warp`` for every code of ``latents [F, latent_size]``: ``{"warp": [F, Gz, Gy, Gx, 4], "min_point", "max_point"}``, one box for
+    all frames -- with a canonical ``bake`` the whole sequence, a handful of tensors ``torch.save`` can write."""
+    lat = torch.as_tensor(latents)
+    if lat.dim() != 2 or lat.shape[0] < 1:
+        raise ValueError(f"latents must be [F >= 1, latent_size], got {tuple(lat.shape)}")
+    frames = [bake_warp(render_kwargs_or_network, lat[i], min_point, max_point, resolution, **kwargs) for i in range(lat.shape[0])]
+    return {"warp": torch.stack([f["warp"] for f in frames], 0), "min_point": frames[0]["min_point"], "max_point": frames[0]["max_point"]}
+
+
+def _warp_parts(warp):
+    """``warp`` (what ``bake_warp`` returns) -> ``(grid [Gz, Gy, Gx, 4] contiguous on the device, lo, hi, (Gx, Gy, Gz))``."""
+    grid = warp["warp"]
+    if not torch.is_tensor(grid) or grid.device.type != "cuda":
+        raise R.Unsupported("the warp is not on a ROCm device")
+    if grid.dim() != 4 or grid.shape[-1] != 4 or grid.dtype not in _VOLUME_DTYPES:
+        raise ValueError(f"a warp is float32 or float16 [Gz, Gy, Gx, 4], got {grid.dtype} {tuple(grid.shape)}")
+    gz, gy, gx = (int(v) for v in grid.shape[:3])
+    if min(gx, gy, gz) < 2 or gx * gy * gz > _lib.VOLUME_MAX_VERTICES:
+        raise ValueError(f"a warp has 2 or more vertices per axis and at most {_lib.VOLUME_MAX_VERTICES} in all, got {(gx, gy, gz)}")
+    lo, hi = grid_extent(warp["min_point"], warp["max_point"])
+    if not (hi > lo).all():
+        raise ValueError(f"a warp needs min < max on every axis, got {lo} .. {hi}")
+    return grid.detach().contiguous(), lo, hi, (gx, gy, gz)
+
+
+def warped_volume_render(volume, warp, rays, *, N_samples, z_vals=None, lindisp=False, white_bkgd=False, rigidity_cutoff=None,
+                         test_time_scaling=None, removal_threshold=None, composite=True, retraw=False, weights=False, alpha=False,
+                         surface=False, return_points=False):
+    """``nrnerf_warped_volume_render`` on tensors: the ``N_samples`` samples ``o + d z`` of every ray bent by ``warp`` (the knobs applied here),
+    the canonical ``volume``'s logits at the bent points, and their compositing -- one kernel.  ``rays [N, >= 8]``; ``z_vals [N, S]`` or the
+    coarse spacing between the rays' near and far.  Returns ``rgb_map / disp_map / acc_map`` (+ ``raw``, ``weights``, ``alpha``,
+    ``surface_pts``, ``surface_rigidity``, ``median_index``, ``points4 [N, S, 4]`` = (bent xyz, rigidity after the cutoff) as asked for);
+    ``composite=False`` runs the lookup alone and returns ``raw`` and / or ``points4``.  The value rule: include/nrnerf.h."""
+    vol, lo, hi, g = _volume_parts(volume)
+    grid, wlo, whi, wg = _warp_parts(warp)
+    dev = vol.device
+    if grid.device != dev:
+        raise ValueError(f"the volume is on {dev}, the warp on {grid.device}")
+    f32 = dict(dtype=torch.float32, device=dev)
+    if rays.dim() != 2 or rays.shape[1] < 8:
+        raise ValueError(f"rays must be [N, >= 8], got {tuple(rays.shape)}")
+    rays = rays.detach().to(**f32).contiguous()
+    N, S = int(rays.shape[0]), int(N_samples)
+    if not 1 <= S <= _lib.MAX_SAMPLES:
+        raise ValueError(f"1 <= N_samples <= {_lib.MAX_SAMPLES}, got {S}")
+    a = _lib.WarpedVolumeRenderArgs()
+    a.struct_size = C.sizeof(_lib.WarpedVolumeRenderArgs)
+    a.n_rays, a.n_samples = N, S
+    a.rays, a.ray_stride = rays.data_ptr() or None, int(rays.shape[1])
+    a.lindisp, a.white_bkgd = int(bool(lindisp)), int(bool(white_bkgd))
+    if z_vals is not None:
+        if tuple(z_vals.shape) != (N, S):
+            raise ValueError(f"z_vals must be {(N, S)}, got {tuple(z_vals.shape)}")
+        z_vals = z_vals.detach().to(**f32).contiguous()
+        a.z = z_vals.data_ptr() or None
+    a.volume, a.volume_dtype = vol.data_ptr(), _VOLUME_DTYPES[vol.dtype]
+    a.g[:] = g
+    a.min_point[:], a.max_point[:] = lo.tolist(), hi.tolist()
+    a.warp, a.warp_dtype = grid.data_ptr(), _VOLUME_DTYPES[grid.dtype]
+    a.warp_g[:] = wg
+    a.warp_min_point[:], a.warp_max_point[:] = wlo.tolist(), whi.tolist()
+    if rigidity_cutoff is not None:
+        a.has_rigidity_cutoff, a.rigidity_cutoff = 1, float(rigidity_cutoff)
+    if test_time_scaling is not None:
+        a.has_test_time_scaling, a.test_time_scaling = 1, float(test_time_scaling)
+    if removal_threshold is not None:
+        a.has_removal_threshold, a.removal_threshold = 1, float(removal_threshold)
+    out = {}
+
+    def new(key, *shape, dtype=torch.float32):
+        out[key] = torch.empty(shape, dtype=dtype, device=dev)
+        return out[key].data_ptr() or None
+
+    if composite:
+        a.rgb, a.disp, a.acc = new("rgb_map", N, 3), new("disp_map", N), new("acc_map", N)
+        if weights:
+            a.weights = new("weights", N, S)
+        if alpha:
+            a.alpha = new("alpha", N, S)
+        if surface:
+            a.surface_pts, a.surface_rigidity = new("surface_pts", N, 3), new("surface_rigidity", N)
+            a.median_index = new("median_index", N, dtype=torch.int32)
+    elif weights or alpha or surface:
+        raise ValueError("weights, alpha and the surface outputs come from compositing")
+    if retraw or (not composite and not return_points):
+        a.raw = new("raw", N, S, 4)
+    if return_points:
+        a.points4 = new("points4", N, S, 4)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().nrnerf_warped_volume_render(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "nrnerf_warped_volume_render")
+    return out
+
+
+def render_baked(volume, warp, rays, *, N_samples=192, z_vals=None, lindisp=False, white_bkgd=False, rigidity_cutoff=None,
+                 test_time_scaling=None, removal_threshold=None, surface=False, retraw=False, return_points=False):
+    """A baked scene rendered along ``rays [N, >= 8]`` with no network, no model handle and no latent code: ``volume`` is the canonical ``bake``,
+    ``warp`` the ``bake_warp`` of the time step.  ``rgb_map / disp_map / acc_map`` (+ ``raw`` under ``retraw``; ``surface_pts``,
+    ``surface_rigidity``, ``median_index`` under ``surface``; ``points4`` under ``return_points``).  The samples are ``N_samples`` of the coarse
+    spacing (``lindisp`` honoured) or ``z_vals [N, S]``.  ``rigidity_cutoff`` (background stabilisation), ``test_time_scaling`` (motion
+    exaggeration) and ``removal_threshold`` are the bender's test-time knobs, applied per sample at render time; ``None`` is off.  Refuses
+    autograd inputs (``Unsupported``): a preview has no gradient."""
+    if not torch.is_tensor(rays) or rays.device.type != "cuda":
+        raise R.Unsupported("rays are not on a ROCm device")
+    if torch.is_grad_enabled() and (rays.requires_grad or volume["raw"].requires_grad or warp["warp"].requires_grad
+                                    or (z_vals is not None and z_vals.requires_grad)):
+        raise R.Unsupported("autograd is enabled (rendering a baked scene has no gradient)")
+    S = int(z_vals.shape[1] if z_vals is not None else N_samples)
+    with torch.no_grad():
+        z = None if z_vals is None else z_vals.detach().to(device=rays.device, dtype=torch.float32).contiguous()
+        return warped_volume_render(volume, warp, rays, N_samples=S, z_vals=z, lindisp=lindisp, white_bkgd=white_bkgd,
+                                    rigidity_cutoff=rigidity_cutoff, test_time_scaling=test_time_scaling, removal_threshold=removal_threshold,
+                                    retraw=retraw, surface=surface, return_points=return_points)
+
+
+def render_baked_frames(volume, warps, render_poses, intrinsics, near, far, **kwargs):
+    """``render_baked`` for every camera of ``render_poses`` (``driver.generate_rays`` per frame): ``(rgbs uint8 [F, H, W, 3], disps float32
+    [F, H, W])`` on the device, ``rgbs`` by the reference's truncating ``to8b`` (run_nerf_helpers.py:19).  ``warps``: what ``bake_warps``
+    returns (``[F, Gz, Gy, Gx, 4]``, one grid per frame; ``[1, ...]`` or what ``bake_warp`` returns: one grid for all frames); ``kwargs``:
+    ``render_baked``'s."""
+    from .driver import generate_rays
+    dev = volume["raw"].device
+    H, W = int(intrinsics["height"]), int(intrinsics["width"])
+    n_frames = len(render_poses)
+    grids = warps["warp"]
+    if not torch.is_tensor(grids) or grids.dim() not in (4, 5):
+        raise ValueError("warps must hold one grid [Gz, Gy, Gx, 4] or a stack [F, Gz, Gy, Gx, 4]")
+    if grids.dim() == 4:
+        grids = grids[None]
+    if grids.shape[0] not in (1, n_frames):
+        raise ValueError(f"warps must hold one grid or one per frame ({n_frames}), got {int(grids.shape[0])}")
+    rgbs = torch.empty((n_frames, H, W, 3), dtype=torch.uint8, device=dev)
+    disps = torch.empty((n_frames, H, W), dtype=torch.float32, device=dev)
+    for i in range(n_frames):
+        rays = generate_rays(render_poses[i], intrinsics, near, far, False, dev)
+        out = render_baked(volume, dict(warps, warp=grids[i if grids.shape[0] > 1 else 0]), rays, **kwargs)
         rgbs[i] = (255 * out["rgb_map"].clamp(0, 1)).to(torch.uint8).view(H, W, 3)          # to8b: clip, scale, truncate
         disps[i] = out["disp_map"].view(H, W)
     return rgbs, disps
