@@ -165,16 +165,7 @@ static hipError_t launch_bwd_epl(const CompositeBwdArgs& a, hipStream_t stream) 
 }
 hipError_t launch_composite_bwd(const CompositeBwdArgs& a, hipStream_t stream) {
     if (a.S < 2 || a.S > MAXS) return hipErrorInvalidValue;
-    switch ((a.S + 63) / 64) {
-        case 1: return launch_bwd_epl<1>(a, stream);
-        case 2: return launch_bwd_epl<2>(a, stream);
-        case 3: return launch_bwd_epl<3>(a, stream);
-        case 4: return launch_bwd_epl<4>(a, stream);
-        case 5: case 6: return launch_bwd_epl<6>(a, stream);
-        case 7: case 8: return launch_bwd_epl<8>(a, stream);
-        case 9: case 10: case 11: case 12: return launch_bwd_epl<12>(a, stream);
-        default: return launch_bwd_epl<16>(a, stream);
-    }
+    return with_epl(a.S, [&](auto epl) { return launch_bwd_epl<epl()>(a, stream); });
 }
 
 template <int EPL>
@@ -219,7 +210,7 @@ __global__ void __launch_bounds__(256) sample_points_kernel(const SamplePointsAr
     const float z = jittered_depth(rp, a.u, idx, i, a.S, a.lindisp);
     a.z_out[idx] = z;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) a.pts_out[idx * 3 + c] = __fadd_rn(rp[c], rounded(rp[3 + c] * z));
+    for (int c = 0; c < 3; ++c) a.pts_out[idx * 3 + c] = __fadd_rn(rp[c], rounded(rp[3 + c] * z));      // sample_point, each store before the next load
 }
 hipError_t launch_sample_points(const SamplePointsArgs& a, hipStream_t stream) {
     const long long n = (long long)a.n_rays * a.S;
@@ -237,17 +228,7 @@ hipError_t launch_zjitter(const JitterArgs& a, hipStream_t stream) {
 hipError_t launch_composite(const CompositeArgs& a, hipStream_t stream) {
     if (a.S < 2 || a.S > MAXS || a.S + a.n_importance > MAXS) return hipErrorInvalidValue;
     if (a.rank_new && a.S + a.n_importance > 256) return hipErrorInvalidValue;      // 8-bit ranks of the split-bender path
-    const int epl = (a.S + 63) / 64;
-    switch (epl) {
-        case 1: return launch_epl<1>(a, stream);
-        case 2: return launch_epl<2>(a, stream);
-        case 3: return launch_epl<3>(a, stream);
-        case 4: return launch_epl<4>(a, stream);
-        case 5: case 6: return launch_epl<6>(a, stream);
-        case 7: case 8: return launch_epl<8>(a, stream);
-        case 9: case 10: case 11: case 12: return launch_epl<12>(a, stream);
-        default: return launch_epl<16>(a, stream);
-    }
+    return with_epl(a.S, [&](auto epl) { return launch_epl<epl()>(a, stream); });
 }
 
 

@@ -56,6 +56,62 @@ __device__ __forceinline__ float wave_scan_mul(float v, int lane) {
     return v;
 }
 
+// ---- the per-sample rules of the per-ray kernels, for every kernel outside this header (nrnerf_volume.hip, nrnerf_warp.hip, whatever comes
+// next).  composite_ray below keeps the text of sample_depth and surface_index inline: with either call in it hipcc emits different code
+// for the kernels with a fused epilogue, the benchmark's hot path; the bit-for-bit tests of tests/test_warp.py and
+// tests/test_volume.py hold the two to each other.
+// depth of sample ic (< S) of `ray` (record at rp): the caller's z, or the coarse spacing between the ray's near and far (train.py:849-852),
+// every product rounded before it is added.  (composite_bwd_kernel and jittered_depth, nrnerf_composite.hip, spell the products __fmul_rn, which
+// the compiler contracts: a different form with different bits, on purpose -- the comment in jittered_depth says why it stays.)
+__device__ __forceinline__ float sample_depth(const CompositeArgs& a, const __attribute__((address_space(1))) float* rp, const int ray, const int ic) {
+    if (a.z) return gmem(a.z)[(size_t)ray * a.S + ic];
+    const float near = rp[6], far = rp[7];
+    const float t = c_lin01(ic, a.S);
+    if (a.lindisp)                                                                       // train.py:850-852
+        return __fdiv_rn(1.0f, __fadd_rn(rounded(__fdiv_rn(1.0f, near) * __fsub_rn(1.0f, t)), rounded(__fdiv_rn(1.0f, far) * t)));
+    return __fadd_rn(rounded(near * __fsub_rn(1.0f, t)), rounded(far * t));              // train.py:849
+}
+
+// p = o + d z, the product rounded before the sum (train.py:871-873: torch's two elementwise launches)
+__device__ __forceinline__ void sample_point(const __attribute__((address_space(1))) float* rp, const float z, float (&p)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c] = __fadd_rn(rp[c], rounded(rp[3 + c] * z));
+}
+
+// the surface pick (free_viewpoint_rendering.py:621-648): index of the sample whose accumulated visibility is closest to 0.5, first one on
+// ties, from the weights composite_ray returned (lane l: samples l * EPL ..); the same value in every lane, always in 0 .. S - 1
+template <int EPL>
+__device__ __forceinline__ int surface_index(const float (&w)[EPL], const int lane, const int S) {
+    // cumsum in strictly sequential order (carry handed from lane to lane): zero-weight plateaus then give
+    // bit-identical prefixes, hence exact ties that resolve to the first index, as with torch.cumsum on the host
+    float carry = 0.f, base = 0.f;
+    for (int l = 0; l < 64; ++l) {
+        float e = carry;
+#pragma unroll
+        for (int k = 0; k < EPL; ++k) e = __fadd_rn(e, w[k]);
+        if (lane == l) base = carry;
+        carry = __shfl(e, l);
+    }
+    // NaN weights (a diverged checkpoint, an overflowed f16 sigma) compare false everywhere: start from this lane's
+    // first valid sample so the index is always in range, like the host argmin the reference uses (fvr:626-628)
+    float best = 3.0e38f, run_c = base;
+    int bidx = (lane * EPL < S) ? lane * EPL : S - 1;
+#pragma unroll
+    for (int k = 0; k < EPL; ++k) {
+        const int i = lane * EPL + k;
+        run_c = __fadd_rn(run_c, w[k]);
+        const float dist = fabsf(__fsub_rn(run_c, 0.5f));
+        if (i < S && dist < best) { best = dist; bidx = i; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bidx, o);
+        if (ob < best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+    }
+    return bidx < 0 ? 0 : (bidx > S - 1 ? S - 1 : bidx);
+}
+
 // what composite_ray reads from HBM before it can start, requested early: out[0..2] = direction, out[3 + k] = depth of sample
 // lane * epl + k (k < epl <= 4; only when the pass has explicit depths)
 __device__ __forceinline__ void composite_prefetch(const CompositeArgs& a, const int ray, const int lane, const int epl, float (&out)[8]) {
@@ -167,14 +223,11 @@ __device__ __forceinline__ void composite_ray(const CompositeArgs& a, const int 
     }
 
     phase_fence();
-    // (warped_render_kernel, nrnerf_warp.hip, keeps its bent points in registers and carries a copy of this block on the weights returned
-    //  in w: a change here is a change there; tests/test_warp.py compares the two bit for bit)
-    // ---- surface reduction: index of the sample whose accumulated visibility is closest to 0.5 (first one on ties),
-    //      and the bent point / rigidity there (free_viewpoint_rendering.py:621-648 does this on the host from the
-    //      full per-sample tensors: ~15 KB/ray of D2H traffic instead of 20 B/ray)
+    // ---- surface reduction: the sample surface_index picks, and the bent point / rigidity there (free_viewpoint_rendering.py:621-648
+    //      does this on the host from the full per-sample tensors: ~15 KB/ray of D2H traffic instead of 20 B/ray).  The text of surface_index,
+    //      inline: calling it here moves instructions in every kernel with a fused epilogue; tests/test_warp.py holds the
+    //      two to the same bits
     if (a.bent4) {
-        // cumsum in strictly sequential order (carry handed from lane to lane): zero-weight plateaus then give
-        // bit-identical prefixes, hence exact ties that resolve to the first index, as with torch.cumsum on the host
         float carry = 0.f, base = 0.f;
         for (int l = 0; l < 64; ++l) {
             float e = carry;
@@ -183,8 +236,6 @@ __device__ __forceinline__ void composite_ray(const CompositeArgs& a, const int 
             if (lane == l) base = carry;
             carry = __shfl(e, l);
         }
-        // NaN weights (a diverged checkpoint, an overflowed f16 sigma) compare false everywhere: start from this lane's
-        // first valid sample so the index is always in range, like the host argmin the reference uses (fvr:626-628)
         float best = 3.0e38f, run_c = base;
         int bidx = (lane * EPL < S) ? lane * EPL : S - 1;
 #pragma unroll

@@ -3,7 +3,32 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace nrn {
+
+// The lane-width table of the per-ray kernels: a wave owns a ray, lane l the EPL consecutive samples l * EPL .. of its S <= 1024, and the
+// kernels are compiled for these eight widths.  with_epl(S, f) calls f(std::integral_constant<int, EPL>{}) with the width of S.
+constexpr int epl_class(int S) {
+    const int n = (S + 63) / 64;
+    return n <= 4 ? n : n <= 6 ? 6 : n <= 8 ? 8 : n <= 12 ? 12 : 16;
+}
+static_assert(epl_class(1) == 1 && epl_class(64) == 1 && epl_class(65) == 2 && epl_class(128) == 2 && epl_class(129) == 3 && epl_class(192) == 3 &&
+              epl_class(193) == 4 && epl_class(256) == 4 && epl_class(257) == 6 && epl_class(384) == 6 && epl_class(385) == 8 && epl_class(512) == 8 &&
+              epl_class(513) == 12 && epl_class(768) == 12 && epl_class(769) == 16 && epl_class(1024) == 16, "the lane-width table");
+template <class F>
+auto with_epl(int S, F&& f) {
+    switch (epl_class(S)) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 12: return f(std::integral_constant<int, 12>{});
+        default: return f(std::integral_constant<int, 16>{});
+    }
+}
 
 // device pointers of one pass' optional per-sample detail outputs (nullable)
 struct SampleOut {

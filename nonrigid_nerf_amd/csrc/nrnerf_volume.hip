@@ -23,32 +23,20 @@ namespace {
 constexpr int VOL_WAVES = 4;            // waves (= rays in flight) per workgroup
 constexpr int VOL_MAXS = 1024;          // NRNERF_MAX_SAMPLES: EPL <= 16
 
-// the logits of sample ic (< S) of `ray`: its point (points4, or o + d z as sample_points_kernel rounds it, z as composite_ray computes it),
+// the logits of sample ic (< S) of `ray`: its point (points4, or sample_point at sample_depth),
 // the lookup, the removal knob
 template <bool HALF>
 __device__ __forceinline__ f32x4 sample_logits(const VolumeArgs& a, const int ray, const int ic) {
     const int S = a.c.S;
-    float px, py, pz, rig = 0.0f;
+    float p[3], rig = 0.0f;
     if (a.points4) {
         const f32x4 q = *(const __attribute__((address_space(1))) f32x4*)(gmem(a.points4) + ((size_t)ray * S + ic) * 4);
-        px = q[0]; py = q[1]; pz = q[2]; rig = q[3];
+        p[0] = q[0]; p[1] = q[1]; p[2] = q[2]; rig = q[3];
     } else {
         const __attribute__((address_space(1))) float* rp = gmem(a.c.rays) + (size_t)ray * a.c.ray_stride;
-        float z;
-        if (a.c.z) z = gmem(a.c.z)[(size_t)ray * S + ic];
-        else {
-            const float near = rp[6], far = rp[7];
-            const float t = c_lin01(ic, S);
-            if (a.c.lindisp)
-                z = __fdiv_rn(1.0f, __fadd_rn(rounded(__fdiv_rn(1.0f, near) * __fsub_rn(1.0f, t)), rounded(__fdiv_rn(1.0f, far) * t)));
-            else
-                z = __fadd_rn(rounded(near * __fsub_rn(1.0f, t)), rounded(far * t));
-        }
-        px = __fadd_rn(rp[0], rounded(rp[3] * z));
-        py = __fadd_rn(rp[1], rounded(rp[4] * z));
-        pz = __fadd_rn(rp[2], rounded(rp[5] * z));
+        sample_point(rp, sample_depth(a.c, rp, ray, ic), p);
     }
-    f32x4 r = volume_at<HALF>(a, px, py, pz);
+    f32x4 r = volume_at<HALF>(a.grid, p[0], p[1], p[2]);
     if (a.has_removal && rig >= a.removal) r[3] = rounded(r[3] * 0.0f);          // rnh:308-311 (a product: NaN stays NaN)
     return r;
 }
@@ -89,7 +77,7 @@ template <int EPL>
 hipError_t launch_epl(const VolumeArgs& a, int num_cus, hipStream_t stream) {
     const long long want = ((long long)a.c.n_rays + VOL_WAVES - 1) / VOL_WAVES, cap = (long long)(num_cus > 0 ? num_cus : 256) * 16;
     const dim3 grid((unsigned)(want < cap ? want : cap));
-    if (a.half) hipLaunchKernelGGL((volume_render_kernel<EPL, true>), grid, dim3(VOL_WAVES * 64), 0, stream, a);
+    if (a.grid.half) hipLaunchKernelGGL((volume_render_kernel<EPL, true>), grid, dim3(VOL_WAVES * 64), 0, stream, a);
     else hipLaunchKernelGGL((volume_render_kernel<EPL, false>), grid, dim3(VOL_WAVES * 64), 0, stream, a);
     return hipGetLastError();
 }
@@ -103,20 +91,11 @@ hipError_t launch_volume_render(const VolumeArgs& a, int num_cus, hipStream_t st
         if (!a.raw_out) return hipErrorInvalidValue;
         const long long want = ((long long)a.c.n_rays * a.c.S + 255) / 256, cap = (long long)(num_cus > 0 ? num_cus : 256) * 32;
         const dim3 grid((unsigned)(want < cap ? want : cap));
-        if (a.half) hipLaunchKernelGGL(volume_lookup_kernel<true>, grid, dim3(256), 0, stream, a);
+        if (a.grid.half) hipLaunchKernelGGL(volume_lookup_kernel<true>, grid, dim3(256), 0, stream, a);
         else hipLaunchKernelGGL(volume_lookup_kernel<false>, grid, dim3(256), 0, stream, a);
         return hipGetLastError();
     }
-    switch ((a.c.S + 63) / 64) {            // samples per lane, as composite_kernel's dispatch
-        case 1: return launch_epl<1>(a, num_cus, stream);
-        case 2: return launch_epl<2>(a, num_cus, stream);
-        case 3: return launch_epl<3>(a, num_cus, stream);
-        case 4: return launch_epl<4>(a, num_cus, stream);
-        case 5: case 6: return launch_epl<6>(a, num_cus, stream);
-        case 7: case 8: return launch_epl<8>(a, num_cus, stream);
-        case 9: case 10: case 11: case 12: return launch_epl<12>(a, num_cus, stream);
-        default: return launch_epl<16>(a, num_cus, stream);
-    }
+    return with_epl(a.c.S, [&](auto epl) { return launch_epl<epl()>(a, num_cus, stream); });
 }
 
 }  // namespace nrn

@@ -1,15 +1,14 @@
 // nrnerf_volume_api.cpp -- the baked-volume entry points of the C ABI (include/nrnerf.h, "ABI 10 (additions): baked volumes"):
 // nrnerf_volume_render (model-free: validate, run the launcher of nrnerf_volume.h on the device that owns the outputs) and nrnerf_bend_points
 // (the bender step of nrnerf_query by itself, on the launchers of nrnerf_bend_points.h).  The checks come in the order the header states them,
-// the ones that need no HIP call first; no entry point keeps state.  Its own unit, so that the objects of the existing entry points are built
-// from unchanged sources.
+// the ones that need no HIP call first; no entry point keeps state.  What nrnerf_volume_render shares with nrnerf_warped_volume_render is in
+// nrnerf_baked_api.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "nrnerf_model.h"
+#include "nrnerf_baked_api.h"
 #include "nrnerf_bend_points.h"
-#include "nrnerf_volume.h"
 
 using namespace nrn;
 
@@ -35,10 +34,8 @@ extern "C" {
 int nrnerf_volume_render(const nrnerf_volume_render_args* a, void* hip_stream) try {
     if (!a || a->struct_size != sizeof(nrnerf_volume_render_args)) return NRNERF_ERR_INVALID;
     if (a->n_rays < 0 || a->n_samples < 1 || a->n_samples > NRNERF_MAX_SAMPLES || a->ray_stride < 8) return NRNERF_ERR_INVALID;
-    for (int c = 0; c < 3; ++c)
-        if (a->g[c] < 2 || !(a->max_point[c] > a->min_point[c])) return NRNERF_ERR_INVALID;                  // (NaN included)
-    if (a->volume_dtype != NRNERF_VOLUME_F32 && a->volume_dtype != NRNERF_VOLUME_F16) return NRNERF_ERR_INVALID;
-    if ((double)a->g[0] * (double)a->g[1] * (double)a->g[2] > (double)(1ll << 30)) return NRNERF_ERR_UNSUPPORTED;      // (in double: three factors below 2^31 overflow 64 bits)
+    if (!grid_ok(a->g, a->min_point, a->max_point, a->volume_dtype)) return NRNERF_ERR_INVALID;
+    if (grid_too_large(a->g)) return NRNERF_ERR_UNSUPPORTED;
     if ((long long)a->n_rays * a->n_samples >= (1ll << 31)) return NRNERF_ERR_UNSUPPORTED;
     if (a->n_rays == 0) return NRNERF_OK;
     if (!a->rays || !a->volume) return NRNERF_ERR_INVALID;
@@ -52,37 +49,19 @@ int nrnerf_volume_render(const nrnerf_volume_render_args* a, void* hip_stream) t
     const void* const owner = maps ? (const void*)a->rgb : (const void*)a->raw;
     int dev = 0;
     if (device_of(owner, dev) != NRNERF_OK) return NRNERF_ERR_INVALID;
-    const void* ptrs[] = {a->rays, a->z, a->points4, a->volume, a->rgb, a->disp, a->acc, a->raw, a->weights, a->alpha,
-                          a->surface_pts, a->surface_rigidity, a->median_index};
-    for (const void* p : ptrs) {
-        int d = 0;
-        if (p && (device_of(p, d) != NRNERF_OK || d != dev)) return NRNERF_ERR_INVALID;
-    }
+    if (!all_on_device({a->rays, a->z, a->points4, a->volume, a->rgb, a->disp, a->acc, a->raw, a->weights, a->alpha,
+                        a->surface_pts, a->surface_rigidity, a->median_index}, dev)) return NRNERF_ERR_INVALID;
     if (a->points4 && ((uintptr_t)a->points4 & 15)) return NRNERF_ERR_INVALID;
     if (a->raw && ((uintptr_t)a->raw & 15)) return NRNERF_ERR_INVALID;
-    if ((uintptr_t)a->volume & (a->volume_dtype == NRNERF_VOLUME_F16 ? 7 : 15)) return NRNERF_ERR_INVALID;
+    if (!grid_aligned(a->volume, a->volume_dtype)) return NRNERF_ERR_INVALID;
     VolumeArgs k{};
-    k.c.rays = a->rays; k.c.ray_stride = a->ray_stride; k.c.z = a->z; k.c.lindisp = a->lindisp; k.c.white_bkgd = a->white_bkgd;
-    k.c.n_rays = a->n_rays; k.c.S = a->n_samples;
-    if (maps) {
-        k.c.rgb = a->rgb; k.c.disp = a->disp; k.c.acc = a->acc; k.c.vis = a->weights; k.c.alpha = a->alpha;
-        if (surface) { k.c.bent4 = a->points4; k.c.surf_pts = a->surface_pts; k.c.surf_rig = a->surface_rigidity; k.c.med_idx = a->median_index; }
-    }
-    k.points4 = a->points4; k.vol = a->volume; k.half = a->volume_dtype == NRNERF_VOLUME_F16;
-    for (int c = 0; c < 3; ++c) {
-        k.g[c] = a->g[c]; k.lo[c] = a->min_point[c];
-        k.top[c] = (float)(a->g[c] - 1);
-        volatile float extent = a->max_point[c] - a->min_point[c];      // (each operation rounded to fp32, whatever the host compiler would like to keep wider)
-        volatile float scale = k.top[c] / extent;
-        k.scale[c] = scale;
-    }
+    k.c = composite_args_of(*a, maps);
+    if (maps && surface) { k.c.bent4 = a->points4; k.c.surf_pts = a->surface_pts; k.c.surf_rig = a->surface_rigidity; k.c.med_idx = a->median_index; }
+    k.points4 = a->points4;
+    k.grid = grid_of(a->volume, a->volume_dtype, a->g, a->min_point, a->max_point);
     k.has_removal = a->has_removal_threshold; k.removal = a->removal_threshold;
     k.raw_out = a->raw;
-    return on_device(dev, [&]() -> int {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return NRNERF_ERR_HIP;
-        return status_of(launch_volume_render(k, cus, (hipStream_t)hip_stream));
-    });
+    return launch_on(dev, k, launch_volume_render, hip_stream);
 } NRN_CATCH
 
 size_t nrnerf_bend_points_workspace_bytes(const nrnerf_model* m) {

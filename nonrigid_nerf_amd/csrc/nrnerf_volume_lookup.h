@@ -1,6 +1,6 @@
 // nrnerf_volume_lookup.h -- the value of a vertex-centred grid of four channels at a point (include/nrnerf.h, "THE VALUE AT A POINT"): device
 // functions shared by nrnerf_volume.hip (the canonical volume at ready-made points) and nrnerf_warp.hip (an offset grid, then the canonical
-// volume at the bent point).  A grid is any record with the members vol / g[3] / lo[3] / scale[3] / top[3] of VolumeArgs.
+// volume at the bent point).  A grid is a GridArgs (nrnerf_volume.h); where a point falls in it is grid_cell, used by both forms of the lookup.
 // Every multiply-add is spelled __fmaf_rn and every product that feeds a sum or a difference goes through rounded(): this build's
 // -ffp-contract=fast would otherwise fuse them per instantiation (nrnerf_composite_ray.h), and every kernel that includes this must give the
 // same bits.
@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "nrnerf_composite_ray.h"
+#include "nrnerf_volume.h"
 
 namespace nrn {
 
@@ -40,13 +41,11 @@ __device__ __forceinline__ void load_pair(const void* vol, const size_t v, f32x4
     }
 }
 
-// the grid's value at (px, py, pz): include/nrnerf.h, "THE VALUE AT A POINT"
-template <bool HALF, class GRID>
-__device__ __forceinline__ f32x4 volume_at(const GRID& a, const float px, const float py, const float pz) {
+// where (px, py, pz) falls in the grid: the cell's lowest corner i and the fractions f in it; ok = false: outside the grid (or NaN), an empty
+// sample.  (ok is an output parameter, not the return value: returned, hipcc allocates up to 4 more VGPRs in warped_render_kernel)
+__device__ __forceinline__ void grid_cell(const GridArgs& a, const float px, const float py, const float pz, int (&i)[3], float (&f)[3], bool& ok) {
     const float p[3] = {px, py, pz};
-    int i[3];
-    float f[3];
-    bool ok = true;
+    ok = true;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float g = rounded(__fsub_rn(p[c], a.lo[c]) * a.scale[c]);
@@ -54,10 +53,19 @@ __device__ __forceinline__ f32x4 volume_at(const GRID& a, const float px, const 
         ok = ok && in;
         const float gs = in ? g : 0.0f;
         int ic = (int)floorf(gs);
-        ic = ic < a.g[c] - 2 ? ic : a.g[c] - 2;              // 0 <= ic <= g - 2: every corner index is inside the volume
+        ic = ic < a.g[c] - 2 ? ic : a.g[c] - 2;              // 0 <= ic <= g - 2: every corner index is inside the grid
         i[c] = ic;
         f[c] = __fsub_rn(gs, (float)ic);
     }
+}
+
+// the grid's value at (px, py, pz): include/nrnerf.h, "THE VALUE AT A POINT"
+template <bool HALF>
+__device__ __forceinline__ f32x4 volume_at(const GridArgs& a, const float px, const float py, const float pz) {
+    int i[3];
+    float f[3];
+    bool ok;
+    grid_cell(a, px, py, pz, i, f, ok);
     f32x4 r = {0.0f, 0.0f, 0.0f, 0.0f};
     if (ok) {
         const size_t gx = (size_t)a.g[0], gxy = gx * (size_t)a.g[1];
@@ -85,23 +93,11 @@ struct GridFetch {
 };
 
 // where the point falls, and the requests for its eight corners (none for an empty sample)
-template <bool HALF, class GRID>
-__device__ __forceinline__ void grid_fetch(const GRID& a, const float px, const float py, const float pz, GridFetch<HALF>& t) {
+template <bool HALF>
+__device__ __forceinline__ void grid_fetch(const GridArgs& a, const float px, const float py, const float pz, GridFetch<HALF>& t) {
     typedef typename GridFetch<HALF>::vertex vertex;
-    const float p[3] = {px, py, pz};
     int i[3];
-    t.ok = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float g = rounded(__fsub_rn(p[c], a.lo[c]) * a.scale[c]);
-        const bool in = g >= 0.0f && g <= a.top[c];          // (NaN: false)
-        t.ok = t.ok && in;
-        const float gs = in ? g : 0.0f;
-        int ic = (int)floorf(gs);
-        ic = ic < a.g[c] - 2 ? ic : a.g[c] - 2;
-        i[c] = ic;
-        t.f[c] = __fsub_rn(gs, (float)ic);
-    }
+    grid_cell(a, px, py, pz, i, t.f, t.ok);
 #pragma unroll
     for (int k = 0; k < 8; ++k) t.c[k] = vertex{};
     if (t.ok) {

@@ -2,18 +2,9 @@
 // No kernel body: the entry point's unit includes this alone.
 #pragma once
 #include "nrnerf_kernels.h"
+#include "nrnerf_volume.h"
 
 namespace nrn {
-
-// a vertex-centred grid of four channels, as VolumeArgs describes its volume
-struct GridArgs {
-    const void* vol;         // [gz,gy,gx,4]
-    int half;                // 0: float32 (16 bytes per vertex), 1: IEEE half (8 bytes per vertex)
-    int g[3];                // gx, gy, gz, each >= 2
-    float lo[3];             // min_point
-    float scale[3];          // (float)(g - 1) / (max_point - min_point), each operation rounded to fp32
-    float top[3];            // (float)(g - 1)
-};
 
 struct WarpArgs {
     // rays / ray_stride / z / lindisp / white_bkgd / n_rays / S / rgb / disp / acc / vis / alpha as composite_kernel reads them; everything

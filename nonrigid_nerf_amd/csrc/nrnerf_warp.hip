@@ -10,8 +10,8 @@
 // requested as soon as it is known, and the canonical interpolations start when all of the group's requests are out.  The corners of a group
 // are GROUP * 64 registers in float32: beyond EPL = 4 the groups are sized so that, next to raw[EPL], every instantiation stays within 256
 // VGPRs and parks nothing in AGPRs.  An empty sample requests nothing.  composite_ray<EPL> then runs on the registers.
-// The surface outputs: composite_ray's reduction reads the bent points from memory, where this kernel has none; it runs here on the weights
-// composite_ray returns (the same operations in the same order), and lane 0 bends the one sample it picks again.
+// The surface outputs: composite_ray reads the bent point of the sample surface_index picks from memory, where this kernel has none; it calls
+// surface_index itself on the weights composite_ray returns, and lane 0 bends the one sample it picks again.
 // warped_lookup_kernel<VHALF, WHALF>: the same per-sample rule, one thread per sample, no compositing.
 // No multiply-add is fused that the rule does not name: every product that feeds a sum goes through rounded() (nrnerf_volume_lookup.h).
 #include <hip/hip_runtime.h>
@@ -26,22 +26,6 @@ namespace {
 
 constexpr int WARP_WAVES = 4;           // waves (= rays in flight) per workgroup
 constexpr int WARP_MAXS = 1024;         // NRNERF_MAX_SAMPLES: EPL <= 16
-
-// depth of sample ic (< S) of the ray at rp, as composite_ray computes it
-__device__ __forceinline__ float sample_depth(const WarpArgs& a, const __attribute__((address_space(1))) float* rp, const int ray, const int ic) {
-    const int S = a.c.S;
-    if (a.c.z) return gmem(a.c.z)[(size_t)ray * S + ic];
-    const float near = rp[6], far = rp[7];
-    const float t = c_lin01(ic, S);
-    if (a.c.lindisp) return __fdiv_rn(1.0f, __fadd_rn(rounded(__fdiv_rn(1.0f, near) * __fsub_rn(1.0f, t)), rounded(__fdiv_rn(1.0f, far) * t)));
-    return __fadd_rn(rounded(near * __fsub_rn(1.0f, t)), rounded(far * t));
-}
-
-// p = o + d z, the product rounded before the sum (sample_points_kernel)
-__device__ __forceinline__ void sample_point(const __attribute__((address_space(1))) float* rp, const float z, float (&p)[3]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) p[c] = __fadd_rn(rp[c], rounded(rp[3 + c] * z));
-}
 
 // (u, m) at p -> (bent xyz, m after the cutoff): rnh:563-570
 __device__ __forceinline__ f32x4 bend(const WarpArgs& a, const float (&p)[3], const f32x4 um) {
@@ -69,7 +53,7 @@ template <bool WHALF>
 __device__ __forceinline__ f32x4 sample_bent(const WarpArgs& a, const int ray, const int ic) {
     const __attribute__((address_space(1))) float* rp = gmem(a.c.rays) + (size_t)ray * a.c.ray_stride;
     float p[3];
-    sample_point(rp, sample_depth(a, rp, ray, ic), p);
+    sample_point(rp, sample_depth(a.c, rp, ray, ic), p);
     return bend(a, p, volume_at<WHALF>(a.warp, p[0], p[1], p[2]));
 }
 
@@ -93,7 +77,7 @@ __global__ void __launch_bounds__(WARP_WAVES * 64) warped_render_kernel(const Wa
 #pragma unroll
             for (int k = 0; k < GROUP; ++k) {
                 const int i = lane * EPL + g0 + k;
-                sample_point(rp, sample_depth(a, rp, ray, i < S ? i : S - 1), p[k]);        // (beyond S: the last sample's, as composite_ray asks for)
+                sample_point(rp, sample_depth(a.c, rp, ray, i < S ? i : S - 1), p[k]);       // (beyond S: the last sample's, as composite_ray asks for)
                 grid_fetch<WHALF>(a.warp, p[k][0], p[k][1], p[k][2], tw[k]);
             }
 #pragma unroll
@@ -117,34 +101,10 @@ __global__ void __launch_bounds__(WARP_WAVES * 64) warped_render_kernel(const Wa
         float z[EPL + 1], w[EPL];
         composite_ray<EPL>(a.c, ray, true, lane, [&](int) { return raw[next++]; }, z, w);
 
-        // ---- the surface reduction of composite_ray (its last block, on the weights it returned): index of the sample whose accumulated
-        //      visibility is closest to 0.5, first one on ties; the bent point and the mask there
+        // ---- the surface outputs: the sample surface_index picks on the weights composite_ray returned, bent again; its bent point and mask
         if (a.surf_pts || a.surf_rig || a.med_idx) {
-            float carry = 0.f, base = 0.f;
-            for (int l = 0; l < 64; ++l) {
-                float e = carry;
-#pragma unroll
-                for (int k = 0; k < EPL; ++k) e = __fadd_rn(e, w[k]);
-                if (lane == l) base = carry;
-                carry = __shfl(e, l);
-            }
-            float best = 3.0e38f, run_c = base;
-            int bidx = (lane * EPL < S) ? lane * EPL : S - 1;
-#pragma unroll
-            for (int k = 0; k < EPL; ++k) {
-                const int i = lane * EPL + k;
-                run_c = __fadd_rn(run_c, w[k]);
-                const float dist = fabsf(__fsub_rn(run_c, 0.5f));
-                if (i < S && dist < best) { best = dist; bidx = i; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ob = __shfl_xor(best, o);
-                const int oi = __shfl_xor(bidx, o);
-                if (ob < best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
-            }
+            const int bidx = surface_index<EPL>(w, lane, S);
             if (lane == 0) {
-                bidx = bidx < 0 ? 0 : (bidx > S - 1 ? S - 1 : bidx);
                 const f32x4 s = sample_bent<WHALF>(a, ray, bidx);
                 if (a.surf_pts) { gmem(a.surf_pts)[(size_t)ray * 3] = s[0]; gmem(a.surf_pts)[(size_t)ray * 3 + 1] = s[1]; gmem(a.surf_pts)[(size_t)ray * 3 + 2] = s[2]; }
                 if (a.surf_rig) gmem(a.surf_rig)[ray] = s[3];
@@ -201,16 +161,7 @@ hipError_t launch_warped_volume_render(const WarpArgs& a, int num_cus, hipStream
             default: return launch(warped_lookup_kernel<true, true>, a, grid, block, stream);
         }
     }
-    switch ((a.c.S + 63) / 64) {            // samples per lane, as composite_kernel's dispatch
-        case 1: return launch_epl<1>(a, num_cus, stream);
-        case 2: return launch_epl<2>(a, num_cus, stream);
-        case 3: return launch_epl<3>(a, num_cus, stream);
-        case 4: return launch_epl<4>(a, num_cus, stream);
-        case 5: case 6: return launch_epl<6>(a, num_cus, stream);
-        case 7: case 8: return launch_epl<8>(a, num_cus, stream);
-        case 9: case 10: case 11: case 12: return launch_epl<12>(a, num_cus, stream);
-        default: return launch_epl<16>(a, num_cus, stream);
-    }
+    return with_epl(a.c.S, [&](auto epl) { return launch_epl<epl()>(a, num_cus, stream); });
 }
 
 }  // namespace nrn

@@ -609,30 +609,25 @@ def bake(render_kwargs, latent=None, min_point=None, max_point=None, resolution=
     return {"raw": vol, "min_point": lo, "max_point": hi}
 
 
-def _volume_parts(volume):
-    """``volume`` (what ``bake`` returns) -> ``(raw [Gz, Gy, Gx, 4] contiguous on the device, lo, hi, (Gx, Gy, Gz))``."""
-    raw = volume["raw"]
-    if not torch.is_tensor(raw) or raw.device.type != "cuda":
-        raise R.Unsupported("the volume is not on a ROCm device")
-    if raw.dim() != 4 or raw.shape[-1] != 4 or raw.dtype not in _VOLUME_DTYPES:
-        raise ValueError(f"a volume is float32 or float16 [Gz, Gy, Gx, 4], got {raw.dtype} {tuple(raw.shape)}")
-    gz, gy, gx = (int(v) for v in raw.shape[:3])
+def _grid_parts(record, key, noun):
+    """``record[key]`` (what ``bake`` / ``bake_warp`` return) -> ``(grid [Gz, Gy, Gx, 4] contiguous on the device, lo, hi, (Gx, Gy, Gz))``."""
+    grid = record[key]
+    if not torch.is_tensor(grid) or grid.device.type != "cuda":
+        raise R.Unsupported(f"the {noun} is not on a ROCm device")
+    if grid.dim() != 4 or grid.shape[-1] != 4 or grid.dtype not in _VOLUME_DTYPES:
+        raise ValueError(f"a {noun} is float32 or float16 [Gz, Gy, Gx, 4], got {grid.dtype} {tuple(grid.shape)}")
+    gz, gy, gx = (int(v) for v in grid.shape[:3])
     if min(gx, gy, gz) < 2 or gx * gy * gz > _lib.VOLUME_MAX_VERTICES:
-        raise ValueError(f"a volume has 2 or more vertices per axis and at most {_lib.VOLUME_MAX_VERTICES} in all, got {(gx, gy, gz)}")
-    lo, hi = grid_extent(volume["min_point"], volume["max_point"])
+        raise ValueError(f"a {noun} has 2 or more vertices per axis and at most {_lib.VOLUME_MAX_VERTICES} in all, got {(gx, gy, gz)}")
+    lo, hi = grid_extent(record["min_point"], record["max_point"])
     if not (hi > lo).all():
-        raise ValueError(f"a volume needs min < max on every axis, got {lo} .. {hi}")
-    return raw.detach().contiguous(), lo, hi, (gx, gy, gz)
+        raise ValueError(f"a {noun} needs min < max on every axis, got {lo} .. {hi}")
+    return grid.detach().contiguous(), lo, hi, (gx, gy, gz)
 
 
-def volume_render(volume, rays, *, N_samples, z_vals=None, points4=None, lindisp=False, white_bkgd=False, removal_threshold=None,
-                  composite=True, retraw=False, weights=False, alpha=False, surface=False):
-    """``nrnerf_volume_render`` on tensors: the volume's logits at the ``N_samples`` samples of every ray -- ``points4 [N, S, 4]`` (xyz, rigidity),
-    or ``o + d z`` -- and their compositing.  ``rays [N, >= 8]``; ``z_vals [N, S]`` or the coarse spacing between the rays' near and far.
-    Returns ``rgb_map / disp_map / acc_map`` (+ ``raw``, ``weights``, ``alpha``, ``surface_pts``, ``surface_rigidity``, ``median_index`` as asked
-    for); ``composite=False`` runs the lookup alone and returns ``raw``.  The sampling rule: include/nrnerf.h."""
-    vol, lo, hi, g = _volume_parts(volume)
-    dev = vol.device
+def _render_front(a, dev, rays, N_samples, z_vals, lindisp, white_bkgd):
+    """The front the two baked-render wrappers share: checks and converts ``rays`` and ``z_vals`` and fills the fields the argument structs
+    ``a`` have in common.  Returns ``(N, S, keep)``; ``keep`` holds the converted tensors, to stay alive over the call."""
     f32 = dict(dtype=torch.float32, device=dev)
     if rays.dim() != 2 or rays.shape[1] < 8:
         raise ValueError(f"rays must be [N, >= 8], got {tuple(rays.shape)}")
@@ -640,8 +635,7 @@ def volume_render(volume, rays, *, N_samples, z_vals=None, points4=None, lindisp
     N, S = int(rays.shape[0]), int(N_samples)
     if not 1 <= S <= _lib.MAX_SAMPLES:
         raise ValueError(f"1 <= N_samples <= {_lib.MAX_SAMPLES}, got {S}")
-    a = _lib.VolumeRenderArgs()
-    a.struct_size = C.sizeof(_lib.VolumeRenderArgs)
+    a.struct_size = C.sizeof(a)
     a.n_rays, a.n_samples = N, S
     a.rays, a.ray_stride = rays.data_ptr() or None, int(rays.shape[1])
     a.lindisp, a.white_bkgd = int(bool(lindisp)), int(bool(white_bkgd))
@@ -650,18 +644,12 @@ def volume_render(volume, rays, *, N_samples, z_vals=None, points4=None, lindisp
             raise ValueError(f"z_vals must be {(N, S)}, got {tuple(z_vals.shape)}")
         z_vals = z_vals.detach().to(**f32).contiguous()
         a.z = z_vals.data_ptr() or None
-    if points4 is not None:
-        if tuple(points4.shape) != (N, S, 4):
-            raise ValueError(f"points4 must be {(N, S, 4)}, got {tuple(points4.shape)}")
-        points4 = points4.detach().to(**f32).contiguous()
-        a.points4 = points4.data_ptr() or None
-    elif removal_threshold is not None or surface:
-        raise ValueError("a removal threshold and the surface outputs need points4")
-    a.volume, a.volume_dtype = vol.data_ptr(), _VOLUME_DTYPES[vol.dtype]
-    a.g[:] = g
-    a.min_point[:], a.max_point[:] = lo.tolist(), hi.tolist()
-    if removal_threshold is not None:
-        a.has_removal_threshold, a.removal_threshold = 1, float(removal_threshold)
+    return N, S, (rays, z_vals)
+
+
+def _render_outputs(a, dev, N, S, composite, weights, alpha, surface):
+    """The back the two wrappers share: the maps, weights, alpha and surface outputs, allocated and named in ``a``.  Returns ``(out, new)``:
+    the dict of results and the allocator ``new(key, *shape)`` that adds to it."""
     out = {}
 
     def new(key, *shape, dtype=torch.float32):
@@ -679,6 +667,32 @@ def volume_render(volume, rays, *, N_samples, z_vals=None, points4=None, lindisp
             a.median_index = new("median_index", N, dtype=torch.int32)
     elif weights or alpha or surface:
         raise ValueError("weights, alpha and the surface outputs come from compositing")
+    return out, new
+
+
+def volume_render(volume, rays, *, N_samples, z_vals=None, points4=None, lindisp=False, white_bkgd=False, removal_threshold=None,
+                  composite=True, retraw=False, weights=False, alpha=False, surface=False):
+    """``nrnerf_volume_render`` on tensors: the volume's logits at the ``N_samples`` samples of every ray -- ``points4 [N, S, 4]`` (xyz, rigidity),
+    or ``o + d z`` -- and their compositing.  ``rays [N, >= 8]``; ``z_vals [N, S]`` or the coarse spacing between the rays' near and far.
+    Returns ``rgb_map / disp_map / acc_map`` (+ ``raw``, ``weights``, ``alpha``, ``surface_pts``, ``surface_rigidity``, ``median_index`` as asked
+    for); ``composite=False`` runs the lookup alone and returns ``raw``.  The sampling rule: include/nrnerf.h."""
+    vol, lo, hi, g = _grid_parts(volume, "raw", "volume")
+    dev = vol.device
+    a = _lib.VolumeRenderArgs()
+    N, S, keep = _render_front(a, dev, rays, N_samples, z_vals, lindisp, white_bkgd)
+    if points4 is not None:
+        if tuple(points4.shape) != (N, S, 4):
+            raise ValueError(f"points4 must be {(N, S, 4)}, got {tuple(points4.shape)}")
+        points4 = points4.detach().to(dtype=torch.float32, device=dev).contiguous()
+        a.points4 = points4.data_ptr() or None
+    elif removal_threshold is not None or surface:
+        raise ValueError("a removal threshold and the surface outputs need points4")
+    a.volume, a.volume_dtype = vol.data_ptr(), _VOLUME_DTYPES[vol.dtype]
+    a.g[:] = g
+    a.min_point[:], a.max_point[:] = lo.tolist(), hi.tolist()
+    if removal_threshold is not None:
+        a.has_removal_threshold, a.removal_threshold = 1, float(removal_threshold)
+    out, new = _render_outputs(a, dev, N, S, composite, weights, alpha, surface)
     if retraw or not composite:
         a.raw = new("raw", N, S, 4)
     with torch.cuda.device(dev):
@@ -862,22 +876,6 @@ def bake_warps(render_kwargs_or_network, latents, min_point=None, max_point=None
     return {"warp": torch.stack([f["warp"] for f in frames], 0), "min_point": frames[0]["min_point"], "max_point": frames[0]["max_point"]}
 
 
-def _warp_parts(warp):
-    """``warp`` (what ``bake_warp`` returns) -> ``(grid [Gz, Gy, Gx, 4] contiguous on the device, lo, hi, (Gx, Gy, Gz))``."""
-    grid = warp["warp"]
-    if not torch.is_tensor(grid) or grid.device.type != "cuda":
-        raise R.Unsupported("the warp is not on a ROCm device")
-    if grid.dim() != 4 or grid.shape[-1] != 4 or grid.dtype not in _VOLUME_DTYPES:
-        raise ValueError(f"a warp is float32 or float16 [Gz, Gy, Gx, 4], got {grid.dtype} {tuple(grid.shape)}")
-    gz, gy, gx = (int(v) for v in grid.shape[:3])
-    if min(gx, gy, gz) < 2 or gx * gy * gz > _lib.VOLUME_MAX_VERTICES:
-        raise ValueError(f"a warp has 2 or more vertices per axis and at most {_lib.VOLUME_MAX_VERTICES} in all, got {(gx, gy, gz)}")
-    lo, hi = grid_extent(warp["min_point"], warp["max_point"])
-    if not (hi > lo).all():
-        raise ValueError(f"a warp needs min < max on every axis, got {lo} .. {hi}")
-    return grid.detach().contiguous(), lo, hi, (gx, gy, gz)
-
-
 def warped_volume_render(volume, warp, rays, *, N_samples, z_vals=None, lindisp=False, white_bkgd=False, rigidity_cutoff=None,
                          test_time_scaling=None, removal_threshold=None, composite=True, retraw=False, weights=False, alpha=False,
                          surface=False, return_points=False):
@@ -886,28 +884,13 @@ def warped_volume_render(volume, warp, rays, *, N_samples, z_vals=None, lindisp=
     coarse spacing between the rays' near and far.  Returns ``rgb_map / disp_map / acc_map`` (+ ``raw``, ``weights``, ``alpha``,
     ``surface_pts``, ``surface_rigidity``, ``median_index``, ``points4 [N, S, 4]`` = (bent xyz, rigidity after the cutoff) as asked for);
     ``composite=False`` runs the lookup alone and returns ``raw`` and / or ``points4``.  The value rule: include/nrnerf.h."""
-    vol, lo, hi, g = _volume_parts(volume)
-    grid, wlo, whi, wg = _warp_parts(warp)
+    vol, lo, hi, g = _grid_parts(volume, "raw", "volume")
+    grid, wlo, whi, wg = _grid_parts(warp, "warp", "warp")
     dev = vol.device
     if grid.device != dev:
         raise ValueError(f"the volume is on {dev}, the warp on {grid.device}")
-    f32 = dict(dtype=torch.float32, device=dev)
-    if rays.dim() != 2 or rays.shape[1] < 8:
-        raise ValueError(f"rays must be [N, >= 8], got {tuple(rays.shape)}")
-    rays = rays.detach().to(**f32).contiguous()
-    N, S = int(rays.shape[0]), int(N_samples)
-    if not 1 <= S <= _lib.MAX_SAMPLES:
-        raise ValueError(f"1 <= N_samples <= {_lib.MAX_SAMPLES}, got {S}")
     a = _lib.WarpedVolumeRenderArgs()
-    a.struct_size = C.sizeof(_lib.WarpedVolumeRenderArgs)
-    a.n_rays, a.n_samples = N, S
-    a.rays, a.ray_stride = rays.data_ptr() or None, int(rays.shape[1])
-    a.lindisp, a.white_bkgd = int(bool(lindisp)), int(bool(white_bkgd))
-    if z_vals is not None:
-        if tuple(z_vals.shape) != (N, S):
-            raise ValueError(f"z_vals must be {(N, S)}, got {tuple(z_vals.shape)}")
-        z_vals = z_vals.detach().to(**f32).contiguous()
-        a.z = z_vals.data_ptr() or None
+    N, S, keep = _render_front(a, dev, rays, N_samples, z_vals, lindisp, white_bkgd)
     a.volume, a.volume_dtype = vol.data_ptr(), _VOLUME_DTYPES[vol.dtype]
     a.g[:] = g
     a.min_point[:], a.max_point[:] = lo.tolist(), hi.tolist()
@@ -920,23 +903,7 @@ def warped_volume_render(volume, warp, rays, *, N_samples, z_vals=None, lindisp=
         a.has_test_time_scaling, a.test_time_scaling = 1, float(test_time_scaling)
     if removal_threshold is not None:
         a.has_removal_threshold, a.removal_threshold = 1, float(removal_threshold)
-    out = {}
-
-    def new(key, *shape, dtype=torch.float32):
-        out[key] = torch.empty(shape, dtype=dtype, device=dev)
-        return out[key].data_ptr() or None
-
-    if composite:
-        a.rgb, a.disp, a.acc = new("rgb_map", N, 3), new("disp_map", N), new("acc_map", N)
-        if weights:
-            a.weights = new("weights", N, S)
-        if alpha:
-            a.alpha = new("alpha", N, S)
-        if surface:
-            a.surface_pts, a.surface_rigidity = new("surface_pts", N, 3), new("surface_rigidity", N)
-            a.median_index = new("median_index", N, dtype=torch.int32)
-    elif weights or alpha or surface:
-        raise ValueError("weights, alpha and the surface outputs come from compositing")
+    out, new = _render_outputs(a, dev, N, S, composite, weights, alpha, surface)
     if retraw or (not composite and not return_points):
         a.raw = new("raw", N, S, 4)
     if return_points:
