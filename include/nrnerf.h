@@ -1148,6 +1148,48 @@ typedef struct nrnerf_warped_volume_render_args {
 } nrnerf_warped_volume_render_args;
 int nrnerf_warped_volume_render(const nrnerf_warped_volume_render_args* args, void* hip_stream);
 
+/* ---- ABI 10 (additions): the adjoint of the lookup -- what refines a baked volume or a baked warp on images.
+ *
+ * THE VALUE AT A POINT above is v = sum over the eight corners k of w_k(f) c_k, the weights w_k the products of f_c and 1 - f_c per axis.
+ * nrnerf_grid_lookup_backward takes M points and the cotangents g_value [M, 4] of their values and returns the two gradients of
+ * sum over the points of <g_value, v> (csrc/nrnerf_grid_grad.h), all in fp32, every operation rounded once:
+ *     the cell i_c and the fractions f_c are THE VALUE AT A POINT's -- one device function serves both directions;
+ *     d_grid[corner k] += w_k * g_value          w_k = ((wx * wy) * wz), wx = f_x or 1 - f_x and likewise for y, z
+ *     d_points[c] = s_c * sum over the channels of g_ch * dv_ch/df_c, channel 0 first, where
+ *         dv/df_x = the differences c_1yz - c_0yz interpolated along y, then z (the same lerp),
+ *         dv/df_y = the differences along y of the forward's x-interpolations, interpolated along z,  dv/df_z likewise along y;
+ *     an EMPTY sample (outside the box, or NaN) adds nothing to d_grid and has d_points = 0.
+ * ONE-SIDED ON A FACE.  The value is continuous but not smooth across a cell face; the derivative returned there is the one of the cell
+ * the forward picks: the upper cell (f_c = 0), on the grid's top face the last cell (f_c = 1).  The weights are then exactly 0 and 1.
+ * Half storage is widened to fp32 first; d_grid is float32 whatever the grid's storage.  tests/grid_grad_reference.py states the rule in
+ * float64.
+ * d_grid is ADDED INTO (the caller zeroes it, or keeps accumulating) with float32 atomic adds to global memory.  THE ORDER OF ITS SUMS IS NOT
+ * FIXED: of the baked family this is the one call without "the same bits on every run" -- two runs differ by the rounding of a reordered
+ * float32 sum.  d_points has one writer per element and a fixed operation order: the same bits on every run, with or without d_grid.
+ * With d_points NULL the grid is not read (`grid` may be NULL); with d_grid NULL nothing is written to a grid.  One kernel per output that is
+ * asked for (d_grid: eight lanes per point, d_points: one thread per point), no LDS, no workspace.  Device pointers only, asynchronous on the
+ * stream, allocates nothing; runs on the device that owns d_grid (d_points when d_grid is NULL).
+ * Checks, in this order: NRNERF_ERR_INVALID for a NULL record or a wrong struct_size; n_points < 0, point_stride < 3; a g < 2, a max_c that is
+ * not > min_c (NaN included), an unknown grid_dtype.  NRNERF_ERR_UNSUPPORTED for more than 2^30 vertices.  Then n_points == 0 answers
+ * NRNERF_OK without a launch.  Then NRNERF_ERR_INVALID for a NULL points / g_value; nothing to write (d_grid and d_points both NULL);
+ * d_points without a grid; and -- the first HIP calls -- memory that is not device memory of one device, a g_value that is not 16-byte
+ * aligned, a grid (when it is read) that is not aligned to one vertex. */
+typedef struct nrnerf_grid_lookup_backward_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_grid_lookup_backward_args) */
+    const void* grid;           /* [gz, gy, gx, 4], float32 or half; read for d_points only */
+    int32_t grid_dtype;         /* NRNERF_VOLUME_F32 / NRNERF_VOLUME_F16 */
+    int32_t g[3];               /* gx, gy, gz, each >= 2 */
+    float min_point[3];         /* the box, as in nrnerf_grid_points; max_c > min_c */
+    float max_point[3];
+    int64_t n_points;           /* M >= 0 */
+    const float* points;        /* [M, point_stride], xyz first */
+    int32_t point_stride;       /* >= 3 */
+    const float* g_value;       /* [M, 4] cotangents of the looked-up values, 16-byte aligned */
+    float* d_grid;              /* in/out float32 [gz, gy, gx, 4], added into, or NULL */
+    float* d_points;            /* out [M, 3], or NULL */
+} nrnerf_grid_lookup_backward_args;
+int nrnerf_grid_lookup_backward(const nrnerf_grid_lookup_backward_args* args, void* hip_stream);
+
 /* Host-only packing (no device needed): writes the MFMA-fragment weight stream + unit table + bias
  * table of one pass exactly as nrnerf_model_create uploads them.  which: 0 = coarse, 1 = fine, 2 = fine without the
  * bender layers, 3 = bender + rigidity layers alone (2, 3: the split-bender path; need a bender and not the exact view directions),

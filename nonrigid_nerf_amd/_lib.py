@@ -387,6 +387,15 @@ class WarpedVolumeRenderArgs(C.Structure):
                 ("points4", C.c_void_p)]
 
 
+class GridLookupBackwardArgs(C.Structure):
+    """nrnerf_grid_lookup_backward_args (ABI 10 additions): the adjoint of the grid lookup -- d grid (added into, float32) and d points from the
+    cotangents of the looked-up values."""
+    _fields_ = [("struct_size", C.c_uint32), ("grid", C.c_void_p), ("grid_dtype", C.c_int32), ("g", C.c_int32 * 3),
+                ("min_point", C.c_float * 3), ("max_point", C.c_float * 3),
+                ("n_points", C.c_int64), ("points", C.c_void_p), ("point_stride", C.c_int32),
+                ("g_value", C.c_void_p), ("d_grid", C.c_void_p), ("d_points", C.c_void_p)]
+
+
 class BendPointsArgs(C.Structure):
     """nrnerf_bend_points_args (ABI 10 additions): the bender step of nrnerf_query by itself, points -> bent4 (bent xyz, rigidity)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_rows", C.c_int32), ("n_samples", C.c_int32),
@@ -449,6 +458,7 @@ EXPORTS = {
     "nrnerf_bender_inverse": (C.c_int, [C.c_void_p, C.POINTER(BenderInverseArgs), C.c_void_p]),
     "nrnerf_volume_render": (C.c_int, [C.POINTER(VolumeRenderArgs), C.c_void_p]),
     "nrnerf_warped_volume_render": (C.c_int, [C.POINTER(WarpedVolumeRenderArgs), C.c_void_p]),
+    "nrnerf_grid_lookup_backward": (C.c_int, [C.POINTER(GridLookupBackwardArgs), C.c_void_p]),
     "nrnerf_bend_points_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "nrnerf_bend_points": (C.c_int, [C.c_void_p, C.POINTER(BendPointsArgs), C.c_void_p]),
     "nrnerf_generate_rays": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -730,7 +730,7 @@ def render_volume(volume, rays, *, network=None, latents=None, N_samples=192, z_
     lat_t = latents if torch.is_tensor(latents) else None
     if torch.is_grad_enabled() and (rays.requires_grad or (lat_t is not None and lat_t.requires_grad) or volume["raw"].requires_grad
                                     or (z_vals is not None and z_vals.requires_grad)):
-        raise R.Unsupported("autograd is enabled (rendering a baked volume has no gradient)")
+        raise R.Unsupported("autograd is enabled (rendering a baked volume has no gradient: render_baked_train has)")
     dev = rays.device
     rays = rays.detach().to(dtype=torch.float32).contiguous()
     N, S = int(rays.shape[0]), int(z_vals.shape[1] if z_vals is not None else N_samples)
@@ -926,7 +926,7 @@ def render_baked(volume, warp, rays, *, N_samples=192, z_vals=None, lindisp=Fals
         raise R.Unsupported("rays are not on a ROCm device")
     if torch.is_grad_enabled() and (rays.requires_grad or volume["raw"].requires_grad or warp["warp"].requires_grad
                                     or (z_vals is not None and z_vals.requires_grad)):
-        raise R.Unsupported("autograd is enabled (rendering a baked scene has no gradient)")
+        raise R.Unsupported("autograd is enabled (rendering a baked scene has no gradient: render_baked_train has)")
     S = int(z_vals.shape[1] if z_vals is not None else N_samples)
     with torch.no_grad():
         z = None if z_vals is None else z_vals.detach().to(device=rays.device, dtype=torch.float32).contiguous()
@@ -959,3 +959,196 @@ def render_baked_frames(volume, warps, render_poses, intrinsics, near, far, **kw
         rgbs[i] = (255 * out["rgb_map"].clamp(0, 1)).to(torch.uint8).view(H, W, 3)          # to8b: clip, scale, truncate
         disps[i] = out["disp_map"].view(H, W)
     return rgbs, disps
+
+
+# --------------------------------------------------------------------------------------------
+# the baked scene under autograd (nrnerf_grid_lookup_backward): refine a baked volume and baked warps on images
+# --------------------------------------------------------------------------------------------
+def _grid_record_fields(a, lo, hi, g):
+    a.g[:] = g
+    a.min_point[:], a.max_point[:] = lo.tolist(), hi.tolist()
+
+
+class _GridLookup(torch.autograd.Function):
+    """``[M, 4]`` values of ``grid [Gz, Gy, Gx, 4]`` at ``points4 [M, 4]`` (xyz first).  Forward: the lookup kernel of ``nrnerf_volume_render``
+    (no maps, the points as ``[M, 1, 4]`` rows); backward: ``nrnerf_grid_lookup_backward``."""
+
+    @staticmethod
+    def forward(ctx, grid, points4, lo, hi):
+        g = tuple(int(v) for v in (grid.shape[2], grid.shape[1], grid.shape[0]))
+        dev = grid.device
+        grid, points4 = grid.detach(), points4.detach()
+        M = int(points4.shape[0])
+        out = torch.empty((M, 4), dtype=torch.float32, device=dev)
+        if M:
+            a = _lib.VolumeRenderArgs()
+            a.struct_size = C.sizeof(a)
+            a.n_rays, a.n_samples = M, 1
+            a.rays, a.ray_stride = points4.data_ptr(), 8          # (device memory the lookup on points4 never reads: the entry point wants a pointer)
+            a.points4 = points4.data_ptr()
+            a.volume, a.volume_dtype = grid.data_ptr(), _VOLUME_DTYPES[grid.dtype]
+            _grid_record_fields(a, lo, hi, g)
+            a.raw = out.data_ptr()
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().nrnerf_volume_render(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "nrnerf_volume_render")
+        ctx.save_for_backward(grid, points4)
+        ctx.lo, ctx.hi, ctx.g = lo, hi, g
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_value):
+        grid, points4 = ctx.saved_tensors
+        want_grid, want_points = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g_value is None or not (want_grid or want_points):
+            return None, None, None, None
+        dev = grid.device
+        M = int(points4.shape[0])
+        g_value = g_value.to(dtype=torch.float32).contiguous()
+        d_grid = torch.zeros(grid.shape, dtype=torch.float32, device=dev) if want_grid else None
+        d_points = torch.zeros((M, 4), dtype=torch.float32, device=dev) if want_points else None
+        d_xyz = torch.empty((M, 3), dtype=torch.float32, device=dev) if want_points else None
+        if M:
+            a = _lib.GridLookupBackwardArgs()
+            a.struct_size = C.sizeof(a)
+            a.grid, a.grid_dtype = grid.data_ptr(), _VOLUME_DTYPES[grid.dtype]
+            _grid_record_fields(a, ctx.lo, ctx.hi, ctx.g)
+            a.n_points, a.points, a.point_stride, a.g_value = M, points4.data_ptr(), 4, g_value.data_ptr()
+            if want_grid:
+                a.d_grid = d_grid.data_ptr()
+            if want_points:
+                a.d_points = d_xyz.data_ptr()
+            with torch.cuda.device(dev):
+                _lib.check(_lib.load().nrnerf_grid_lookup_backward(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                           "nrnerf_grid_lookup_backward")
+            if want_points:
+                d_points[:, :3] = d_xyz
+        return (d_grid.to(grid.dtype) if want_grid else None), d_points, None, None
+
+
+def grid_lookup(grid, min_point, max_point, points):
+    """The value of a vertex-centred grid ``[Gz, Gy, Gx, 4]`` (float32 or float16, on the device) at ``points [..., 3]`` (or ``[..., 4]``, xyz
+    first): ``[..., 4]`` float32 by THE VALUE AT A POINT of include/nrnerf.h -- the bits of ``volume_render(composite=False)`` -- and
+    differentiable with respect to ``grid`` and ``points`` (``nrnerf_grid_lookup_backward``).  A point outside the box, or NaN, has value 0 and
+    no gradient; on a cell face the gradient is the one of the cell the lookup picks (the upper cell, the last one on the top face).  The
+    gradient of ``grid`` is summed in float32 with atomic adds -- its last bits can differ between runs -- and cast to the grid's dtype once."""
+    if not torch.is_tensor(grid) or grid.device.type != "cuda":
+        raise R.Unsupported("the grid is not on a ROCm device")
+    _, lo, hi, _ = _grid_parts({"grid": grid, "min_point": min_point, "max_point": max_point}, "grid", "grid")
+    if not torch.is_tensor(points) or points.dim() < 1 or points.shape[-1] not in (3, 4):
+        raise ValueError(f"points must be [..., 3] or [..., 4], got {tuple(points.shape) if torch.is_tensor(points) else type(points)}")
+    lead = tuple(points.shape[:-1])
+    p = points.to(device=grid.device, dtype=torch.float32).reshape(-1, points.shape[-1])
+    if p.shape[-1] == 3:
+        p = torch.cat([p, torch.zeros_like(p[:, :1])], -1)
+    if int(p.shape[0]) >= 1 << 31:
+        raise ValueError("at most 2^31 - 1 points per call")
+    return _GridLookup.apply(grid.contiguous(), p.contiguous(), lo, hi).reshape(lead + (4,))
+
+
+def render_baked_train(volume, warp, rays, *, N_samples, z_vals=None, lindisp=False, white_bkgd=False, rigidity_cutoff=None,
+                       test_time_scaling=None, removal_threshold=None):
+    """``render_baked``'s value rule under autograd, with respect to ``volume["raw"]`` and / or ``warp["warp"]`` (whichever requires a gradient):
+    ``{"rgb_map", "disp_map", "acc_map", "weights"}``, the forward bits of ``render_baked``.  Composed of tested parts: the depths
+    (``sample_rays``, or ``z_vals [N, S]``), ``p = o + d z``, ``grid_lookup`` of the warp, the cutoff (a decision: no gradient passes through
+    it), ``p + m u`` (times the scaling), ``grid_lookup`` of the volume, the removal factor, then the compositing kernels of the training step
+    (``training._Composite``).  ``warp=None``: straight rays (the knobs have nothing to act on and must be ``None``).  Rays and depths carry no
+    gradient."""
+    from .training import _Composite
+    if not torch.is_tensor(rays) or rays.device.type != "cuda":
+        raise R.Unsupported("rays are not on a ROCm device")
+    _, lo, hi, _ = _grid_parts(volume, "raw", "volume")
+    dev = volume["raw"].device
+    if warp is not None:
+        _, wlo, whi, _ = _grid_parts(warp, "warp", "warp")
+        if warp["warp"].device != dev:
+            raise ValueError(f"the volume is on {dev}, the warp on {warp['warp'].device}")
+    elif rigidity_cutoff is not None or test_time_scaling is not None or removal_threshold is not None:
+        raise ValueError("the bender's knobs need a warp")
+    if rays.dim() != 2 or rays.shape[1] < 8:
+        raise ValueError(f"rays must be [N, >= 8], got {tuple(rays.shape)}")
+    f32 = dict(dtype=torch.float32, device=dev)
+    rays = rays.detach().to(**f32).contiguous()
+    N, S = int(rays.shape[0]), int(z_vals.shape[1] if z_vals is not None else N_samples)
+    if not 1 <= S <= _lib.MAX_SAMPLES:
+        raise ValueError(f"1 <= N_samples <= {_lib.MAX_SAMPLES}, got {S}")
+    with torch.no_grad():
+        pts = None
+        if z_vals is not None:
+            if tuple(z_vals.shape) != (N, S):
+                raise ValueError(f"z_vals must be {(N, S)}, got {tuple(z_vals.shape)}")
+            z = z_vals.detach().to(**f32).contiguous()
+        elif S >= 2:
+            z, pts = sample_rays(rays, S, lindisp)
+        else:       # one sample: the near bound
+            z = (1.0 / (1.0 / rays[:, 6:7])).contiguous() if lindisp else rays[:, 6:7].contiguous()
+        if pts is None:
+            pts = rays[:, None, 0:3] + rays[:, None, 3:6] * z[..., None]                # a product and a sum, each rounded, as the kernels'
+    if warp is not None:
+        um = grid_lookup(warp["warp"], wlo, whi, pts)
+        u, m = um[..., :3], um[..., 3]
+        if rigidity_cutoff is not None:
+            m = torch.where(m.detach() <= torch.tensor(float(rigidity_cutoff), **f32), torch.zeros_like(m), m)      # rnh:563-564
+        off = m[..., None] * u                                                                                        # rnh:567
+        if test_time_scaling is not None:
+            off = off * torch.tensor(float(test_time_scaling), **f32)                                                 # rnh:568-569
+        bent = pts + off
+    else:
+        bent = pts
+    raw = grid_lookup(volume["raw"], lo, hi, bent)
+    if removal_threshold is not None:
+        kill = m.detach() >= torch.tensor(float(removal_threshold), **f32)                                            # rnh:308-311
+        raw = torch.cat([raw[..., :3], torch.where(kill, raw[..., 3] * 0.0, raw[..., 3])[..., None]], -1)
+    rgb, disp, acc, weights = _Composite.apply(raw, rays, z, None, bool(white_bkgd), 0, None)[:4]
+    return {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "weights": weights}
+
+
+def refine_bake(volume, warps, frames, *, steps, lr, batch_rays=None, params=("volume",), optimizer="adam", seed=0, **render):
+    """Refines a baked scene on images: ``steps`` iterations of Adam (``optimizer="sgd"``: plain gradient descent) at rate ``lr`` on the mean
+    squared error of ``render_baked_train``'s ``rgb_map`` against target colours.  ``frames``: a sequence of ``(rays [R, >= 8], target rgb
+    [R, 3], warp index)``; step ``k`` takes frame ``k mod len(frames)`` and of it ``batch_rays`` rays drawn without replacement by a generator
+    seeded with ``seed`` (``None``: all of its rays, in order).  ``warps``: what ``bake_warps`` / ``bake_warp`` returns (``[F, Gz, Gy, Gx, 4]`` or
+    one grid, which every index then means), or ``None`` for straight rays.  ``params``: ``"volume"`` and / or ``"warp"``, what is refined; the
+    refined grids are kept in float32 during the loop and come back in their records' dtype.  ``render``: ``render_baked_train``'s keywords
+    (``N_samples``, ``lindisp``, ``white_bkgd``, the knobs).  Returns ``(volume record, warps record or None, [loss per step])``; the inputs are
+    not modified.  No scheduler, no checkpointing."""
+    params = tuple(params)
+    if not params or any(k not in ("volume", "warp") for k in params):
+        raise ValueError(f"params names 'volume' and / or 'warp', got {params}")
+    if "warp" in params and warps is None:
+        raise ValueError("there is no warp to refine")
+    if optimizer not in ("adam", "sgd"):
+        raise ValueError(f"optimizer is 'adam' or 'sgd', got {optimizer!r}")
+    if len(frames) < 1:
+        raise ValueError("refine_bake needs at least one frame")
+    dev = volume["raw"].device
+    vol = volume["raw"].detach().to(torch.float32).clone().requires_grad_("volume" in params)
+    grids = None
+    if warps is not None:
+        grids = warps["warp"]
+        if not torch.is_tensor(grids) or grids.dim() not in (4, 5):
+            raise ValueError("warps must hold one grid [Gz, Gy, Gx, 4] or a stack [F, Gz, Gy, Gx, 4]")
+        grids = grids.detach().to(torch.float32).clone().requires_grad_("warp" in params)
+    leaves = [t for t in (vol, grids) if t is not None and t.requires_grad]
+    opt = torch.optim.Adam(leaves, lr=lr) if optimizer == "adam" else torch.optim.SGD(leaves, lr=lr)
+    gen = torch.Generator().manual_seed(int(seed))
+    losses = []
+    for k in range(int(steps)):
+        rays, target, index = frames[k % len(frames)]
+        rays, target = rays.to(device=dev, dtype=torch.float32), target.to(device=dev, dtype=torch.float32)
+        if batch_rays is not None and int(batch_rays) < int(rays.shape[0]):
+            pick = torch.randperm(int(rays.shape[0]), generator=gen)[:int(batch_rays)].to(dev)
+            rays, target = rays[pick], target[pick]
+        w = None
+        if grids is not None:
+            w = dict(warps, warp=grids if grids.dim() == 4 else grids[int(index) if grids.shape[0] > 1 else 0])
+        out = render_baked_train(dict(volume, raw=vol), w, rays, **render)
+        loss = ((out["rgb_map"] - target) ** 2).mean()
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        losses.append(loss.detach())
+    history = torch.stack(losses).cpu().tolist() if losses else []
+    new_volume = dict(volume, raw=vol.detach().to(volume["raw"].dtype))
+    new_warps = None if warps is None else dict(warps, warp=grids.detach().to(warps["warp"].dtype))
+    return new_volume, new_warps, history
