@@ -1190,6 +1190,84 @@ typedef struct nrnerf_grid_lookup_backward_args {
 } nrnerf_grid_lookup_backward_args;
 int nrnerf_grid_lookup_backward(const nrnerf_grid_lookup_backward_args* args, void* hip_stream);
 
+/* ---- ABI 10 (additions): view-dependent bakes -- the colour logits of a view-dependent head as low-order real spherical harmonics per vertex.
+ *
+ * The density of a view-dependent head is a function of position, its colour one of position and direction.  A bake keeps, per vertex, the
+ * MEAN of the colour logits over directions in the volume above (`raw`: a valid volume for every call above, which then renders the
+ * direction-averaged colour) and, next to it, the coefficients of the real spherical harmonics of degree 1 .. L, L = 1 or 2 (csrc/
+ * nrnerf_sh_volume.h).
+ *
+ * THE COEFFICIENTS.  A second array on the volume's grid -- the same box, the same resolution, the same dtype -- row-major sh [Gz, Gy, Gx, C],
+ * C = 12 for L = 1 and 24 for L = 2: the coefficient of basis function k = 1 .. K - 1, K = (L + 1)^2, and colour c at channel 3 (k - 1) + c; for
+ * L = 1 the channels 9 .. 11 are zero and never read.  A vertex's channels are contiguous; the base is aligned to four channels.
+ * THE BASIS at a direction d = (x, y, z), in fp32, every product rounded once before anything is added to it:
+ *     Y1 = 0.4886025119029199 * (-y)      Y2 = 0.4886025119029199 * z       Y3 = 0.4886025119029199 * (-x)
+ *     Y4 = 1.0925484305920792 * (x * y)   Y5 = -1.0925484305920792 * (y * z)   Y7 = -1.0925484305920792 * (x * z)
+ *     Y6 = 0.31539156525252005 * ((2 * (z * z) - (x * x)) - (y * y))      Y8 = 0.5462742152960396 * ((x * x) - (y * y))
+ * (Y0 = 0.28209479177387814 is carried by `raw`: the mean IS Y0 times the coefficient of k = 0.)
+ * THE COLOUR LOGIT OF A SAMPLE, colour c:   acc = raw_c;   for k = 1 .. K - 1 in this order:  acc = fma(Y_k(d), v_{k,c}, acc)
+ * where raw is the volume at the sample's bent point by THE VALUE AT A POINT and v the sh array there by the same rule -- the same cell i_c,
+ * the same fractions f_c, the same lerp per channel, half widened first.  An EMPTY sample (outside the box, or NaN) has raw = 0 and v = 0.
+ * The sigma logit and the removal knob are those of nrnerf_warped_volume_render; the compositing is that call's, unedited.
+ * THE BENT POINT (b, m) OF A SAMPLE: with `warp` the rule of nrnerf_warped_volume_render (knobs included); with `points4_in` the caller's
+ * points4_in[n, i] (e.g. nrnerf_bend_points' bent4); with neither the straight sample p = o + d z and m = 0.
+ * THE DIRECTION OF A SAMPLE, `direction_mode`:
+ *     NRNERF_SH_DIRECTION_DIFFERENCES (the reference's rule for a head behind a bender, run_nerf_helpers.py:339-351), over the bent points of
+ *         the ray, empty or not:  for i >= 1  e = b_i - b_{i-1},  n = sqrt(((e_x * e_x) + (e_y * e_y)) + (e_z * e_z)),  d_i = e / (n + 1e-6);
+ *         d_0 = d_1.  Needs n_samples >= 2.
+ *     NRNERF_SH_DIRECTION_RAY (the reference's viewdirs of a network without bender):  e = the ray's direction (columns 3 .. 5), n as above,
+ *         d = e / n for every sample of the ray.
+ * raw [N, S, 4] holds (the three colour logits after the sum, the sigma logit after the removal knob); points4 [N, S, 4] = (b, m).  This call
+ * on its own points4 through points4_in returns the warp path's bits.  With rgb, disp and acc all NULL nothing is composited: raw and / or
+ * points4 alone are written by a one-thread-per-sample kernel, the render kernel's bits.  One kernel, no workspace, no atomics, no device
+ * counter: the same bits on every run.  Device pointers only, asynchronous on the stream, allocates nothing; runs on the device that owns rgb
+ * (raw, else points4, when nothing is composited).  sh_degree 0 is served by the calls above on `raw`.
+ * Checks, in this order: NRNERF_ERR_INVALID for a NULL record or a wrong struct_size; n_rays < 0, n_samples outside 1 .. NRNERF_MAX_SAMPLES,
+ * ray_stride < 8; sh_degree other than 1 or 2; an unknown direction_mode; DIFFERENCES with n_samples == 1; a warp together with points4_in;
+ * the volume's g < 2, max_c not > min_c (NaN included), unknown volume_dtype; with a warp, the same three of the warp.
+ * NRNERF_ERR_UNSUPPORTED for more than 2^30 vertices in either grid or 2^31 or more samples.  Then n_rays == 0 answers NRNERF_OK without a
+ * launch.  Then NRNERF_ERR_INVALID for a NULL rays / volume / sh; rgb, disp, acc neither all given nor all NULL; nothing to write (no maps,
+ * no raw and no points4); weights / alpha / a surface output without the maps; and -- the first HIP calls -- memory that is not device memory
+ * of one device, a raw / points4 / points4_in that is not 16-byte aligned, a grid that is not aligned to four channels. */
+enum { NRNERF_SH_DIRECTION_DIFFERENCES = 0, NRNERF_SH_DIRECTION_RAY = 1 };
+typedef struct nrnerf_sh_volume_render_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_sh_volume_render_args) */
+    int32_t n_rays, n_samples;  /* N >= 0, 1 <= S <= NRNERF_MAX_SAMPLES (DIFFERENCES: 2 <= S) */
+    const float* rays;          /* [N, ray_stride]: o (0..2), d (3..5), near, far (6, 7) */
+    int32_t ray_stride;         /* >= 8 */
+    int32_t lindisp;            /* the coarse spacing linear in inverse depth; read when z is NULL */
+    const float* z;             /* [N, S] sample depths, or NULL: the coarse spacing */
+    const void* volume;         /* [gz, gy, gx, 4] logits: the mean colour over directions, sigma; float32 or half */
+    int32_t volume_dtype;       /* NRNERF_VOLUME_F32 / NRNERF_VOLUME_F16: of `volume` and of `sh` */
+    int32_t g[3];               /* gx, gy, gz, each >= 2 */
+    float min_point[3];         /* the volume's box, as in nrnerf_grid_points; max_c > min_c */
+    float max_point[3];
+    const void* warp;           /* [wgz, wgy, wgx, 4] (unmasked offset xyz, rigidity mask), float32 or half, or NULL: no warp */
+    int32_t warp_dtype;         /* NRNERF_VOLUME_F32 / NRNERF_VOLUME_F16; the four warp fields are read with a warp only */
+    int32_t warp_g[3];
+    float warp_min_point[3];
+    float warp_max_point[3];
+    int32_t has_rigidity_cutoff;    float rigidity_cutoff;      /* the knobs of nrnerf_render_args; these two act on a warp only */
+    int32_t has_test_time_scaling;  float test_time_scaling;
+    int32_t white_bkgd;
+    int32_t has_removal_threshold; float removal_threshold;     /* on m: the warp's mask after the cutoff, points4_in's w, 0 on straight rays */
+    float* rgb;                 /* out [N, 3] */
+    float* disp;                /* out [N] */
+    float* acc;                 /* out [N] */
+    float* raw;                 /* out [N, S, 4] the samples' logits (colour after the sum, sigma after the removal knob), or NULL */
+    float* weights;             /* out [N, S] or NULL */
+    float* alpha;               /* out [N, S] or NULL */
+    float* surface_pts;         /* out [N, 3] or NULL */
+    float* surface_rigidity;    /* out [N] or NULL */
+    int32_t* median_index;      /* out [N] or NULL */
+    float* points4;             /* out [N, S, 4] (bent xyz, m), 16-byte aligned, or NULL */
+    const void* sh;             /* [gz, gy, gx, 12 * sh_degree] coefficients, the dtype of `volume` */
+    int32_t sh_degree;          /* 1 or 2 */
+    const float* points4_in;    /* [N, S, 4] ready-made bent points (xyz, m), 16-byte aligned, or NULL; not together with a warp */
+    int32_t direction_mode;     /* NRNERF_SH_DIRECTION_DIFFERENCES / NRNERF_SH_DIRECTION_RAY */
+} nrnerf_sh_volume_render_args;
+int nrnerf_sh_volume_render(const nrnerf_sh_volume_render_args* args, void* hip_stream);
+
 /* Host-only packing (no device needed): writes the MFMA-fragment weight stream + unit table + bias
  * table of one pass exactly as nrnerf_model_create uploads them.  which: 0 = coarse, 1 = fine, 2 = fine without the
  * bender layers, 3 = bender + rigidity layers alone (2, 3: the split-bender path; need a bender and not the exact view directions),

@@ -387,6 +387,17 @@ class WarpedVolumeRenderArgs(C.Structure):
                 ("points4", C.c_void_p)]
 
 
+class ShVolumeRenderArgs(C.Structure):
+    """nrnerf_sh_volume_render_args (ABI 10 additions): nrnerf_warped_volume_render_args' fields, then the spherical-harmonic coefficients of a
+    view-dependent bake, its degree, optional ready-made bent points and the rule a sample's direction comes from."""
+    _fields_ = WarpedVolumeRenderArgs._fields_ + [("sh", C.c_void_p), ("sh_degree", C.c_int32), ("points4_in", C.c_void_p),
+                                                  ("direction_mode", C.c_int32)]
+
+
+SH_DIRECTION_DIFFERENCES, SH_DIRECTION_RAY = 0, 1       # NRNERF_SH_DIRECTION_DIFFERENCES / NRNERF_SH_DIRECTION_RAY
+SH_MAX_DEGREE = 2
+
+
 class GridLookupBackwardArgs(C.Structure):
     """nrnerf_grid_lookup_backward_args (ABI 10 additions): the adjoint of the grid lookup -- d grid (added into, float32) and d points from the
     cotangents of the looked-up values."""
@@ -459,6 +470,7 @@ EXPORTS = {
     "nrnerf_volume_render": (C.c_int, [C.POINTER(VolumeRenderArgs), C.c_void_p]),
     "nrnerf_warped_volume_render": (C.c_int, [C.POINTER(WarpedVolumeRenderArgs), C.c_void_p]),
     "nrnerf_grid_lookup_backward": (C.c_int, [C.POINTER(GridLookupBackwardArgs), C.c_void_p]),
+    "nrnerf_sh_volume_render": (C.c_int, [C.POINTER(ShVolumeRenderArgs), C.c_void_p]),
     "nrnerf_bend_points_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "nrnerf_bend_points": (C.c_int, [C.c_void_p, C.POINTER(BendPointsArgs), C.c_void_p]),
     "nrnerf_generate_rays": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),

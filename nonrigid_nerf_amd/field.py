@@ -545,8 +545,52 @@ def volume_grid_shape(resolution):
     return g
 
 
+def _lebedev_26():
+    """The 26-point Lebedev rule on the sphere, exact to degree 7: ``(directions [26, 3], weights [26])`` in float64, the weights summing to 1
+    (the integral over the sphere is ``4 pi sum_d w_d f(d)``).  Six axis directions (1/21), twelve edge directions (4/105), eight corner
+    directions (9/280), in this fixed order: the order ``bake`` accumulates in."""
+    axes = [(s if c == 0 else 0.0, s if c == 1 else 0.0, s if c == 2 else 0.0) for c in range(3) for s in (1.0, -1.0)]
+    edges = [tuple(0.0 if c == skip else (s0 if c == (skip + 1) % 3 else s1) for c in range(3))
+             for skip in (2, 0, 1) for s0 in (1.0, -1.0) for s1 in (1.0, -1.0)]
+    corners = [(sx, sy, sz) for sx in (1.0, -1.0) for sy in (1.0, -1.0) for sz in (1.0, -1.0)]
+    d = np.asarray(axes + edges + corners, dtype=np.float64)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    w = np.asarray([1.0 / 21.0] * 6 + [4.0 / 105.0] * 12 + [9.0 / 280.0] * 8, dtype=np.float64)
+    return d, w
+
+
+SH_DIRECTIONS, SH_WEIGHTS = _lebedev_26()
+_SH_C0, _SH_C1, _SH_C2, _SH_C20, _SH_C22 = 0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396
+
+
+def sh_channels(degree: int) -> int:
+    """Channels per vertex of the ``"sh"`` array of a bake of ``degree`` 1 or 2: 12 (9 coefficients and 3 zeros) or 24.  Pure."""
+    if degree not in (1, 2):
+        raise ValueError(f"an sh array has degree 1 or 2, got {degree!r}")
+    return 12 * degree
+
+
+def sh_basis(dirs, degree):
+    """The real spherical harmonics ``Y_0 .. Y_{K-1}``, ``K = (degree + 1)^2``, at directions ``dirs [..., 3]`` (float32 or float64 tensor; the
+    result has its dtype): ``[..., K]`` in the order and with the operation order of include/nrnerf.h ("view-dependent bakes").  Pure."""
+    degree = int(degree)
+    if not 0 <= degree <= _lib.SH_MAX_DEGREE:
+        raise ValueError(f"sh_degree is 0 .. {_lib.SH_MAX_DEGREE}, got {degree}")
+    d = torch.as_tensor(dirs)
+    if d.dtype not in (torch.float32, torch.float64) or d.shape[-1] != 3:
+        raise ValueError(f"dirs must be float32 or float64 [..., 3], got {d.dtype} {tuple(d.shape)}")
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    out = [torch.full_like(x, _SH_C0)]
+    if degree >= 1:
+        out += [_SH_C1 * -y, _SH_C1 * z, _SH_C1 * -x]
+    if degree >= 2:
+        xx, yy, zz = x * x, y * y, z * z
+        out += [_SH_C2 * (x * y), -_SH_C2 * (y * z), _SH_C20 * ((2.0 * zz - xx) - yy), -_SH_C2 * (x * z), _SH_C22 * (xx - yy)]
+    return torch.stack(out, -1)
+
+
 def bake(render_kwargs, latent=None, min_point=None, max_point=None, resolution=128, *, fine=True, with_bending=False, dtype=torch.float32,
-         rows_per_launch=None, precision=None, checkpoint=None):
+         rows_per_launch=None, precision=None, checkpoint=None, sh_degree=None):
     """The field's raw outputs on a regular grid, kept as LOGITS: ``{"raw": [Gz, Gy, Gx, 4] (r, g, b, sigma before the sigmoid / relu),
     "min_point", "max_point"}`` -- what ``render_volume`` interpolates.  ``sample_grid``'s slab loop (``nrnerf_grid_points`` -> ``nrnerf_query``)
     writing the first four raw channels instead of going through ``nrnerf_field_from_raw``; the result does not depend on ``rows_per_launch``.
@@ -555,12 +599,34 @@ def bake(render_kwargs, latent=None, min_point=None, max_point=None, resolution=
     bender is applied to the samples at render time.  ``with_bending=True`` bakes the observed space of ONE time step (``latent``); the
     time-conditioned baseline always bakes per code.  ``dtype``: ``torch.float32`` or ``torch.float16`` (the float32 bake rounded once; 8 bytes
     per vertex).  ``resolution``: an int or ``(Gx, Gy, Gz)``, each 2 .. ``MAX_SAMPLES``.  The extent defaults to the checkpoint's volume extent.
-    A view-dependent head raises ``Unsupported``: its colour is not a function of position."""
+    A view-dependent head raises ``Unsupported``: its colour is not a function of position -- unless ``sh_degree`` says how to keep the
+    dependence.
+
+    ``sh_degree = L`` in 0 .. 2 (a view-dependent head only; ``ValueError`` on any other): the colour logits are projected onto the real
+    spherical harmonics of degree <= L with the 26-point Lebedev rule (``SH_DIRECTIONS``, ``SH_WEIGHTS``; exact to degree 7, so the nine
+    functions are orthonormal under it) -- one pass of the slab loop per direction, every vertex queried with that direction.  The record:
+    ``"raw"`` = (the MEAN colour logits over the directions, the sigma logit of the first direction), a valid volume for every call that takes
+    one (it renders the direction-averaged colour); ``"sh" [Gz, Gy, Gx, 12 L]`` (``L >= 1``) = the coefficients of basis function ``k = 1 ..
+    (L + 1)^2 - 1`` of colour ``c`` at channel ``3 (k - 1) + c`` (``L = 1``: channels 9 .. 11 are zero), in ``dtype``; ``"sh_degree": L``.
+    ``raw_c = sum_d w_d f_c(d)`` and ``sh_{k,c} = sum_d (4 pi w_d Y_k(d)) f_c(d)``, accumulated in float32 in the order of the direction table,
+    rounded to ``dtype`` once.  ``render_volume`` / ``render_baked`` evaluate the sum at each sample's direction (``sh_volume_render``).  Behind a
+    ray bender the head's direction comes from its row neighbours (rnh:339-351), which a grid vertex does not have: ``with_bending=True``
+    stays ``Unsupported`` there -- bake the canonical volume and render it through a warp."""
     if dtype not in _VOLUME_DTYPES:
         raise ValueError(f"a baked volume is float32 or float16, got {dtype}")
     net = render_kwargs.get("network_fine") if fine and render_kwargs.get("network_fine") is not None else render_kwargs["network_fn"]
-    if bool(getattr(net, "use_viewdirs", False)):
-        raise R.Unsupported("a view-dependent head cannot be baked: its colour is not a function of position")
+    views = bool(getattr(net, "use_viewdirs", False))
+    if sh_degree is not None:
+        if isinstance(sh_degree, bool) or not isinstance(sh_degree, (int, np.integer)) or not 0 <= int(sh_degree) <= _lib.SH_MAX_DEGREE:
+            raise ValueError(f"sh_degree is None or 0 .. {_lib.SH_MAX_DEGREE}, got {sh_degree!r}")
+        if not views:
+            raise ValueError("sh_degree is for a view-dependent head: this one's colour is a function of position, bake it without")
+        sh_degree = int(sh_degree)
+        if with_bending and R._bender_of(net) is not None:
+            raise R.Unsupported("a view-dependent head behind a ray bender takes its direction from a sample's row neighbours, which a grid "
+                                "vertex does not have: bake the canonical volume (with_bending=False)")
+    elif views:
+        raise R.Unsupported("a view-dependent head cannot be baked: its colour is not a function of position (sh_degree keeps the dependence)")
     if min_point is None or max_point is None:
         from .visualize import volume_extent_of
         ext = volume_extent_of(checkpoint) if checkpoint is not None else None
@@ -594,19 +660,59 @@ def bake(render_kwargs, latent=None, min_point=None, max_point=None, resolution=
     rows_max = max(n for _, n in slabs)
     pts = torch.empty((rows_max, gx, 4), dtype=torch.float32, device=dev)
     raw = torch.empty((rows_max, gx, ch), dtype=torch.float32, device=dev)
+    sh = sh_rows = None
+    if sh_degree is not None:
+        if model.has_bender:
+            raise R.Unsupported("a view-dependent head behind a ray bender cannot be baked per time step: bake the canonical volume")
+        basis = sh_basis(torch.from_numpy(SH_DIRECTIONS), sh_degree)                                           # float64 [26, K]
+        dirs = torch.from_numpy(SH_DIRECTIONS).to(device=dev, dtype=torch.float32).contiguous()
+        weights = torch.from_numpy(SH_WEIGHTS).to(device=dev, dtype=torch.float32)
+        coef = (4.0 * np.pi * torch.from_numpy(SH_WEIGHTS)[:, None] * basis[:, 1:]).to(device=dev, dtype=torch.float32)     # [26, K - 1]
+        n_coef = int(coef.shape[1])
+        acc_raw = torch.empty((rows_max, gx, 4), dtype=torch.float32, device=dev)
+        if sh_degree >= 1:
+            sh = torch.empty((gz, gy, gx, sh_channels(sh_degree)), dtype=dtype, device=dev)
+            sh_rows = sh.view(n_rows, gx, sh_channels(sh_degree))
+            acc_sh = torch.empty((rows_max, gx, sh_channels(sh_degree) // 3, 3), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev), torch.no_grad():
         for first, n in slabs:
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             _lib.check(lib.nrnerf_grid_points(lo.ctypes.data_as(fp), hi.ctypes.data_as(fp), gx, gy, gz, first, n, pts.data_ptr(), stream),
                        "nrnerf_grid_points")
-            try:
-                model.query(pts[:n], None if lat is None else lat.expand(n, -1), None, 0, out={"raw": raw[:n]}, **knobs)
-            except _lib.NrnerfError as e:
-                if e.status != _lib.ERR_UNSUPPORTED:
-                    raise
-                raise R.Unsupported(str(e)) from e
-            vol_rows[first:first + n].copy_(raw[:n, :, :4])
-    return {"raw": vol, "min_point": lo, "max_point": hi}
+            if sh_degree is None:
+                try:
+                    model.query(pts[:n], None if lat is None else lat.expand(n, -1), None, 0, out={"raw": raw[:n]}, **knobs)
+                except _lib.NrnerfError as e:
+                    if e.status != _lib.ERR_UNSUPPORTED:
+                        raise
+                    raise R.Unsupported(str(e)) from e
+                vol_rows[first:first + n].copy_(raw[:n, :, :4])
+                continue
+            # one query per direction, the same direction for every vertex of the slab; per vertex the sums run in the table's order
+            acc_raw[:n].zero_()
+            if sh_rows is not None:
+                acc_sh[:n].zero_()
+            for d in range(len(SH_WEIGHTS)):
+                try:
+                    model.query(pts[:n], None if lat is None else lat.expand(n, -1), dirs[d:d + 1].expand(n, -1), 0, out={"raw": raw[:n]}, **knobs)
+                except _lib.NrnerfError as e:
+                    if e.status != _lib.ERR_UNSUPPORTED:
+                        raise
+                    raise R.Unsupported(str(e)) from e
+                if d == 0:
+                    acc_raw[:n, :, 3].copy_(raw[:n, :, 3])
+                acc_raw[:n, :, :3].add_(raw[:n, :, :3] * weights[d])
+                if sh_rows is not None:
+                    acc_sh[:n, :, :n_coef].add_(raw[:n, :, None, :3] * coef[d][:, None])
+            vol_rows[first:first + n].copy_(acc_raw[:n])
+            if sh_rows is not None:
+                sh_rows[first:first + n].copy_(acc_sh[:n].view(n, gx, -1))
+    if sh_degree is None:
+        return {"raw": vol, "min_point": lo, "max_point": hi}
+    record = {"raw": vol, "sh_degree": sh_degree, "min_point": lo, "max_point": hi}
+    if sh is not None:
+        record["sh"] = sh
+    return record
 
 
 def _grid_parts(record, key, noun):
@@ -724,7 +830,9 @@ def render_volume(volume, rays, *, network=None, latents=None, N_samples=192, z_
     ``nrnerf_bend_points`` -- the modules' knobs (``rigidity_test_time_cutoff``, ``test_time_scaling``, and the removal threshold unless
     ``removal_threshold`` is given) as ``query_points`` reads them -- and looked up at the bent points: any time step, motion exaggeration and
     background stabilisation included, from one bake.  Without ``network`` (or without a bender): straight rays, no bender launch -- a bake of
-    one time step's observed space, or a static scene.  Refuses autograd inputs (``Unsupported``): a preview has no gradient."""
+    one time step's observed space, or a static scene.  Refuses autograd inputs (``Unsupported``): a preview has no gradient.
+    A volume record with ``"sh"`` (``bake(sh_degree=1 or 2)`` of a view-dependent head) goes through ``sh_volume_render`` instead: the colour
+    of a sample is evaluated at its direction -- the difference of consecutive bent points behind a bender, the ray's direction without."""
     if rays.device.type != "cuda":
         raise R.Unsupported("rays are not on a ROCm device")
     lat_t = latents if torch.is_tensor(latents) else None
@@ -767,10 +875,13 @@ def render_volume(volume, rays, *, network=None, latents=None, N_samples=192, z_
                 if e.status != _lib.ERR_UNSUPPORTED:
                     raise
                 raise R.Unsupported(str(e)) from e
-        elif surface:
+        elif surface and not _has_sh(volume):
             points4 = torch.cat([pts, torch.zeros_like(pts[..., :1])], -1)
         if points4 is None:
             removal_threshold = None
+        if _has_sh(volume):         # a view-dependent bake: bent points give the directions by differences, straight rays their own
+            return sh_volume_render(volume, rays, N_samples=S, z_vals=z, points4=points4, lindisp=lindisp, white_bkgd=white_bkgd,
+                                    removal_threshold=removal_threshold, retraw=retraw, surface=surface)
         return volume_render(volume, rays, N_samples=S, z_vals=z, points4=points4, lindisp=lindisp, white_bkgd=white_bkgd,
                              removal_threshold=removal_threshold, retraw=retraw, surface=surface)
 
@@ -914,6 +1025,81 @@ def warped_volume_render(volume, warp, rays, *, N_samples, z_vals=None, lindisp=
     return out
 
 
+def _has_sh(volume) -> bool:
+    """Whether a volume record carries spherical-harmonic coefficients (a view-dependent bake of degree >= 1)."""
+    return isinstance(volume, dict) and volume.get("sh") is not None
+
+
+def _sh_parts(volume, vol):
+    """``volume["sh"]`` checked against the record's ``"raw"`` (``vol``, as ``_grid_parts`` returned it): ``(sh contiguous, degree)``."""
+    sh = volume["sh"]
+    if not torch.is_tensor(sh) or sh.device != vol.device:
+        raise R.Unsupported("the sh array is not on the volume's device")
+    degree = volume.get("sh_degree", int(sh.shape[-1]) // 12 if sh.dim() == 4 else None)
+    if degree not in (1, 2):
+        raise ValueError(f"an sh array has sh_degree 1 or 2, got {degree!r}")
+    want = tuple(vol.shape[:3]) + (sh_channels(int(degree)),)
+    if tuple(sh.shape) != want or sh.dtype != vol.dtype:
+        raise ValueError(f"the sh array of this volume is {vol.dtype} {want}, got {sh.dtype} {tuple(sh.shape)}")
+    return sh.detach().contiguous(), int(degree)
+
+
+def sh_volume_render(volume, rays, *, N_samples, warp=None, points4=None, z_vals=None, lindisp=False, white_bkgd=False, rigidity_cutoff=None,
+                     test_time_scaling=None, removal_threshold=None, composite=True, retraw=False, weights=False, alpha=False,
+                     surface=False, return_points=False, ray_directions=None):
+    """``nrnerf_sh_volume_render`` on tensors: ``warped_volume_render`` for a volume record with ``"sh"`` (``bake(sh_degree=1 or 2)``) -- per
+    sample the colour logits are ``raw`` plus the spherical harmonics at the sample's direction times the coefficients at the bent point.
+    The bent points are ``warp``'s (a ``bake_warp`` record; the knobs applied here), the ready-made ``points4 [N, S, 4]`` (not with a warp),
+    or the straight samples.  ``ray_directions``: ``True`` takes every sample's direction from its ray, ``False`` from the difference of
+    consecutive bent points (needs 2 samples or more); ``None`` picks differences whenever a warp or ``points4`` is given, as the reference
+    does for a head behind a bender.  Outputs and the other arguments: ``warped_volume_render``'s.  The value rule: include/nrnerf.h."""
+    vol, lo, hi, g = _grid_parts(volume, "raw", "volume")
+    sh, degree = _sh_parts(volume, vol)
+    dev = vol.device
+    if warp is not None and points4 is not None:
+        raise ValueError("a warp bends the samples itself: points4 cannot be given with it")
+    a = _lib.ShVolumeRenderArgs()
+    N, S, keep = _render_front(a, dev, rays, N_samples, z_vals, lindisp, white_bkgd)
+    a.volume, a.volume_dtype = vol.data_ptr(), _VOLUME_DTYPES[vol.dtype]
+    a.g[:] = g
+    a.min_point[:], a.max_point[:] = lo.tolist(), hi.tolist()
+    a.sh, a.sh_degree = sh.data_ptr(), degree
+    if warp is not None:
+        grid, wlo, whi, wg = _grid_parts(warp, "warp", "warp")
+        if grid.device != dev:
+            raise ValueError(f"the volume is on {dev}, the warp on {grid.device}")
+        a.warp, a.warp_dtype = grid.data_ptr(), _VOLUME_DTYPES[grid.dtype]
+        a.warp_g[:] = wg
+        a.warp_min_point[:], a.warp_max_point[:] = wlo.tolist(), whi.tolist()
+    elif rigidity_cutoff is not None or test_time_scaling is not None:
+        raise ValueError("the rigidity cutoff and the scaling act on a warp")
+    if points4 is not None:
+        if tuple(points4.shape) != (N, S, 4):
+            raise ValueError(f"points4 must be {(N, S, 4)}, got {tuple(points4.shape)}")
+        points4 = points4.detach().to(dtype=torch.float32, device=dev).contiguous()
+        a.points4_in = points4.data_ptr() or None
+    if ray_directions is None:
+        ray_directions = warp is None and points4 is None
+    if not ray_directions and S < 2:
+        raise ValueError("a direction from the difference of bent points needs 2 samples or more")
+    a.direction_mode = _lib.SH_DIRECTION_RAY if ray_directions else _lib.SH_DIRECTION_DIFFERENCES
+    if rigidity_cutoff is not None:
+        a.has_rigidity_cutoff, a.rigidity_cutoff = 1, float(rigidity_cutoff)
+    if test_time_scaling is not None:
+        a.has_test_time_scaling, a.test_time_scaling = 1, float(test_time_scaling)
+    if removal_threshold is not None:
+        a.has_removal_threshold, a.removal_threshold = 1, float(removal_threshold)
+    out, new = _render_outputs(a, dev, N, S, composite, weights, alpha, surface)
+    if retraw or (not composite and not return_points):
+        a.raw = new("raw", N, S, 4)
+    if return_points:
+        a.points4 = new("points4", N, S, 4)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().nrnerf_sh_volume_render(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "nrnerf_sh_volume_render")
+    return out
+
+
 def render_baked(volume, warp, rays, *, N_samples=192, z_vals=None, lindisp=False, white_bkgd=False, rigidity_cutoff=None,
                  test_time_scaling=None, removal_threshold=None, surface=False, retraw=False, return_points=False):
     """A baked scene rendered along ``rays [N, >= 8]`` with no network, no model handle and no latent code: ``volume`` is the canonical ``bake``,
@@ -921,7 +1107,8 @@ def render_baked(volume, warp, rays, *, N_samples=192, z_vals=None, lindisp=Fals
     ``surface_rigidity``, ``median_index`` under ``surface``; ``points4`` under ``return_points``).  The samples are ``N_samples`` of the coarse
     spacing (``lindisp`` honoured) or ``z_vals [N, S]``.  ``rigidity_cutoff`` (background stabilisation), ``test_time_scaling`` (motion
     exaggeration) and ``removal_threshold`` are the bender's test-time knobs, applied per sample at render time; ``None`` is off.  Refuses
-    autograd inputs (``Unsupported``): a preview has no gradient."""
+    autograd inputs (``Unsupported``): a preview has no gradient.  A volume record with ``"sh"`` (a view-dependent bake) goes through
+    ``sh_volume_render``: the colour of a sample is evaluated at the difference of the ray's consecutive bent points."""
     if not torch.is_tensor(rays) or rays.device.type != "cuda":
         raise R.Unsupported("rays are not on a ROCm device")
     if torch.is_grad_enabled() and (rays.requires_grad or volume["raw"].requires_grad or warp["warp"].requires_grad
@@ -930,6 +1117,10 @@ def render_baked(volume, warp, rays, *, N_samples=192, z_vals=None, lindisp=Fals
     S = int(z_vals.shape[1] if z_vals is not None else N_samples)
     with torch.no_grad():
         z = None if z_vals is None else z_vals.detach().to(device=rays.device, dtype=torch.float32).contiguous()
+        if _has_sh(volume):         # a view-dependent bake: the same kernel with a colour per direction (differences of the bent points)
+            return sh_volume_render(volume, rays, warp=warp, N_samples=S, z_vals=z, lindisp=lindisp, white_bkgd=white_bkgd,
+                                    rigidity_cutoff=rigidity_cutoff, test_time_scaling=test_time_scaling, removal_threshold=removal_threshold,
+                                    retraw=retraw, surface=surface, return_points=return_points)
         return warped_volume_render(volume, warp, rays, N_samples=S, z_vals=z, lindisp=lindisp, white_bkgd=white_bkgd,
                                     rigidity_cutoff=rigidity_cutoff, test_time_scaling=test_time_scaling, removal_threshold=removal_threshold,
                                     retraw=retraw, surface=surface, return_points=return_points)
@@ -1031,7 +1222,10 @@ def grid_lookup(grid, min_point, max_point, points):
     first): ``[..., 4]`` float32 by THE VALUE AT A POINT of include/nrnerf.h -- the bits of ``volume_render(composite=False)`` -- and
     differentiable with respect to ``grid`` and ``points`` (``nrnerf_grid_lookup_backward``).  A point outside the box, or NaN, has value 0 and
     no gradient; on a cell face the gradient is the one of the cell the lookup picks (the upper cell, the last one on the top face).  The
-    gradient of ``grid`` is summed in float32 with atomic adds -- its last bits can differ between runs -- and cast to the grid's dtype once."""
+    gradient of ``grid`` is summed in float32 with atomic adds -- its last bits can differ between runs -- and cast to the grid's dtype once.
+    A volume record with ``"sh"`` in place of ``grid`` raises ``Unsupported``: gradients of spherical-harmonic coefficients are out of scope."""
+    if _has_sh(grid):
+        raise R.Unsupported("a volume record with spherical-harmonic coefficients: gradients of the coefficients are out of scope")
     if not torch.is_tensor(grid) or grid.device.type != "cuda":
         raise R.Unsupported("the grid is not on a ROCm device")
     _, lo, hi, _ = _grid_parts({"grid": grid, "min_point": min_point, "max_point": max_point}, "grid", "grid")
@@ -1055,6 +1249,8 @@ def render_baked_train(volume, warp, rays, *, N_samples, z_vals=None, lindisp=Fa
     (``training._Composite``).  ``warp=None``: straight rays (the knobs have nothing to act on and must be ``None``).  Rays and depths carry no
     gradient."""
     from .training import _Composite
+    if _has_sh(volume):
+        raise R.Unsupported("a view-dependent bake has no gradient: gradients of spherical-harmonic coefficients are out of scope")
     if not torch.is_tensor(rays) or rays.device.type != "cuda":
         raise R.Unsupported("rays are not on a ROCm device")
     _, lo, hi, _ = _grid_parts(volume, "raw", "volume")
@@ -1111,7 +1307,10 @@ def refine_bake(volume, warps, frames, *, steps, lr, batch_rays=None, params=("v
     one grid, which every index then means), or ``None`` for straight rays.  ``params``: ``"volume"`` and / or ``"warp"``, what is refined; the
     refined grids are kept in float32 during the loop and come back in their records' dtype.  ``render``: ``render_baked_train``'s keywords
     (``N_samples``, ``lindisp``, ``white_bkgd``, the knobs).  Returns ``(volume record, warps record or None, [loss per step])``; the inputs are
-    not modified.  No scheduler, no checkpointing."""
+    not modified.  No scheduler, no checkpointing.  A volume record with ``"sh"`` (a view-dependent bake) raises ``Unsupported``: gradients of
+    the coefficients are out of scope."""
+    if _has_sh(volume):
+        raise R.Unsupported("a view-dependent bake cannot be refined: gradients of spherical-harmonic coefficients are out of scope")
     params = tuple(params)
     if not params or any(k not in ("volume", "warp") for k in params):
         raise ValueError(f"params names 'volume' and / or 'warp', got {params}")
