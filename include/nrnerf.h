@@ -1268,6 +1268,114 @@ typedef struct nrnerf_sh_volume_render_args {
 } nrnerf_sh_volume_render_args;
 int nrnerf_sh_volume_render(const nrnerf_sh_volume_render_args* args, void* hip_stream);
 
+/* ---- ABI 10 (additions): occupancy masks -- a baked render that asks for nothing where the volume is empty.
+ *
+ * Every sample inside the box costs the eight corners of `raw` and of every chunk of `sh`, and most of a scene's box is empty.  Whether a
+ * cell is empty can be read off the record alone: the compositing takes s = max(sigma, 0), alpha = 1 - exp(-s * dist), weight = alpha * T, and
+ * THE VALUE AT A POINT's lerp fma(f, b, fma(-f, a, a)) with f in [0, 1] is, in both steps, the monotone rounding of a value between a and b;
+ * so where all eight corners of a cell carry a sigma logit <= 0 the interpolated sigma is <= 0 at every point of the cell (the removal knob
+ * multiplies it by 0: still <= 0), its alpha is exactly +0 and its weight exactly +0 -- the sample adds exactly nothing to rgb, disp, acc,
+ * the weights, alpha or the surface pick.  A mask marks such cells by the block; a sample whose cell lies in an EMPTY block is treated as
+ * the value rule's EMPTY sample (raw = 0, v = 0, nothing requested), as a sample outside the box already is (csrc/nrnerf_occupancy.h,
+ * csrc/nrnerf_culled_volume.h).
+ *
+ * THE MASK of a volume of g_c vertices (g_c - 1 cells) per axis:
+ *     BLOCKS.  A block is 2^k cells per axis, k = occupancy_log2_block in 1 .. 4 (8 cells by default in the Python layer);
+ *         nb_c = ceil((g_c - 1) / 2^k) blocks per axis.
+ *     THE BLOCK OF A CELL.  Cell i_c (THE VALUE AT A POINT clamps it to 0 .. g_c - 2) lies in block i_c >> k: always a valid block.
+ *     VERTEX RANGE.  Block (bx, by, bz) covers the vertices b_c * 2^k .. min(b_c * 2^k + 2^k, g_c - 1) inclusive on each axis: every corner
+ *         of every one of its cells (the faces it shares with its upper neighbours included).
+ *     OCCUPIED.  A block is occupied iff some vertex of that range has a sigma logit (channel 3 of `raw`) that is NOT <= threshold (NaN
+ *         counts as occupied), or any of its four `raw` channels is not finite: a -inf sigma, or a NaN colour under weight zero, would
+ *         otherwise turn a NaN of the unmasked render into a number.  (The `sh` array is not read: the caller vouches that it is finite.)
+ *     threshold = 0 is the EXACT mode above; threshold > 0 culls lossily (a block whose every vertex has a sigma logit <= threshold
+ *         is dropped, thin as it is, not empty); a negative or NaN threshold is refused.
+ *     STORAGE.  One bit per block, bit index (bz * nb_y + by) * nb_x + bx, in 32-bit words: word index >> 5, bit index & 31, the unused high
+ *         bits of the last word zero; ceil(nb_x * nb_y * nb_z / 32) words.  A 256^3 volume at k = 3 is 4 KiB.
+ * A mask is a snapshot of the volume it was built from: after the volume changes it is rebuilt.
+ *
+ * nrnerf_occupancy_build: the words of a volume's mask.  One kernel, one wave per word (one writer per word), no workspace, no atomics: the
+ * same bits on every run.  Device pointers only, asynchronous on the stream, allocates nothing; runs on the device that owns `words`.
+ * Checks, in this order: NRNERF_ERR_INVALID for a NULL record or a wrong struct_size; a g < 2, an unknown volume_dtype; log2_block outside
+ * 1 .. 4; a threshold that is negative or NaN.  NRNERF_ERR_UNSUPPORTED for more than 2^30 vertices.  NRNERF_ERR_INVALID for an n_words that is
+ * not nrnerf_occupancy_words(g, log2_block); a NULL volume / words; and -- the first HIP calls -- memory that is not device memory of one
+ * device, a volume that is not aligned to one vertex, words that are not 4-byte aligned. */
+typedef struct nrnerf_occupancy_build_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_occupancy_build_args) */
+    const void* volume;         /* [gz, gy, gx, 4] logits, float32 or half */
+    int32_t volume_dtype;       /* NRNERF_VOLUME_F32 / NRNERF_VOLUME_F16 */
+    int32_t g[3];               /* gx, gy, gz, each >= 2 */
+    int32_t log2_block;         /* k: 1 .. 4 */
+    float threshold;            /* >= 0; 0: the exact mode */
+    int32_t* words;             /* out [n_words] */
+    int64_t n_words;            /* nrnerf_occupancy_words(g, log2_block) */
+} nrnerf_occupancy_build_args;
+/* ceil(nb_x * nb_y * nb_z / 32); 0 for a NULL g, a g < 2 or a log2_block outside 1 .. 4.  Host only, no HIP call */
+int64_t nrnerf_occupancy_words(const int32_t* g, int32_t log2_block);
+int nrnerf_occupancy_build(const nrnerf_occupancy_build_args* args, void* hip_stream);
+
+/* nrnerf_culled_volume_render: nrnerf_sh_volume_render -- the same three point sources (a warp, points4_in, straight rays), every knob,
+ * every output, the same value rule, the same kernels' mapping -- with a mask of the volume: after the cell of a sample's bent point is
+ * found, the bit of the cell's block is ANDed into the sample's "not empty" flag before anything is requested.  Nothing else differs: the
+ * directions come from the bent points, not from the cells; the surface outputs bend the picked sample again.
+ * With a mask built at threshold 0 from the same finite record: rgb, disp, acc, weights, alpha, the surface outputs, the median index and
+ * points4 are the bits of the unmasked call; `raw` holds the unmasked call's bits at samples in occupied blocks and the empty sample's (zeros,
+ * whatever the removal knob) at the skipped ones.
+ * sh == NULL with sh_degree == 0 is the degree-0 record, `raw` alone, rendered as nrnerf_warped_volume_render / nrnerf_volume_render render
+ * it (direction_mode is checked and otherwise unused, n_samples == 1 is allowed).  occupancy == NULL is refused: the calls above serve that
+ * case.  The record has no noise input, and the kernels' launcher refuses a compositing record that carries one: noise added to sigma voids
+ * the criterion.  One kernel, no workspace, no atomics, no device counter: the same bits on every run.  Device pointers only, asynchronous
+ * on the stream, allocates nothing; runs on the device that owns rgb (raw, else points4, when nothing is composited).
+ * Checks, in this order: NRNERF_ERR_INVALID for a NULL record or a wrong struct_size; n_rays < 0, n_samples outside 1 .. NRNERF_MAX_SAMPLES,
+ * ray_stride < 8; sh_degree outside 0 .. 2; an unknown direction_mode; DIFFERENCES with n_samples == 1 at sh_degree 1 / 2; a warp together
+ * with points4_in; the volume's g < 2, max_c not > min_c (NaN included), unknown volume_dtype; with a warp, the same three of the warp;
+ * occupancy_log2_block outside 1 .. 4.  NRNERF_ERR_UNSUPPORTED for more than 2^30 vertices in either grid or 2^31 or more samples.
+ * NRNERF_ERR_INVALID for an occupancy_words that is not nrnerf_occupancy_words(g, occupancy_log2_block).  Then n_rays == 0 answers NRNERF_OK
+ * without a launch.  Then NRNERF_ERR_INVALID for a NULL rays / volume; a NULL occupancy; sh given at sh_degree 0 or NULL at sh_degree 1 / 2;
+ * rgb, disp, acc neither all given nor all NULL; nothing to write (no maps, no raw and no points4); weights / alpha / a surface output
+ * without the maps; and -- the first HIP calls -- memory that is not device memory of one device (the mask included), a raw / points4 /
+ * points4_in that is not 16-byte aligned, a grid that is not aligned to four channels, a mask that is not 4-byte aligned. */
+typedef struct nrnerf_culled_volume_render_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_culled_volume_render_args) */
+    int32_t n_rays, n_samples;  /* the fields of nrnerf_sh_volume_render_args, in its order, read the same way */
+    const float* rays;
+    int32_t ray_stride;
+    int32_t lindisp;
+    const float* z;
+    const void* volume;
+    int32_t volume_dtype;
+    int32_t g[3];
+    float min_point[3];
+    float max_point[3];
+    const void* warp;
+    int32_t warp_dtype;
+    int32_t warp_g[3];
+    float warp_min_point[3];
+    float warp_max_point[3];
+    int32_t has_rigidity_cutoff;    float rigidity_cutoff;
+    int32_t has_test_time_scaling;  float test_time_scaling;
+    int32_t white_bkgd;
+    int32_t has_removal_threshold; float removal_threshold;
+    float* rgb;
+    float* disp;
+    float* acc;
+    float* raw;
+    float* weights;
+    float* alpha;
+    float* surface_pts;
+    float* surface_rigidity;
+    int32_t* median_index;
+    float* points4;
+    const void* sh;             /* or NULL with sh_degree 0 */
+    int32_t sh_degree;          /* 0, 1 or 2 */
+    const float* points4_in;
+    int32_t direction_mode;
+    const int32_t* occupancy;   /* [occupancy_words] the mask of `volume`'s grid (nrnerf_occupancy_build) */
+    int32_t occupancy_log2_block;   /* k the mask was built with: 1 .. 4 */
+    int64_t occupancy_words;    /* nrnerf_occupancy_words(g, occupancy_log2_block) */
+} nrnerf_culled_volume_render_args;
+int nrnerf_culled_volume_render(const nrnerf_culled_volume_render_args* args, void* hip_stream);
+
 /* Host-only packing (no device needed): writes the MFMA-fragment weight stream + unit table + bias
  * table of one pass exactly as nrnerf_model_create uploads them.  which: 0 = coarse, 1 = fine, 2 = fine without the
  * bender layers, 3 = bender + rigidity layers alone (2, 3: the split-bender path; need a bender and not the exact view directions),

@@ -398,6 +398,34 @@ SH_DIRECTION_DIFFERENCES, SH_DIRECTION_RAY = 0, 1       # NRNERF_SH_DIRECTION_DI
 SH_MAX_DEGREE = 2
 
 
+class OccupancyBuildArgs(C.Structure):
+    """nrnerf_occupancy_build_args (ABI 10 additions): the occupancy mask of a baked volume, one bit per block of 2^log2_block cells per axis."""
+    _fields_ = [("struct_size", C.c_uint32), ("volume", C.c_void_p), ("volume_dtype", C.c_int32), ("g", C.c_int32 * 3),
+                ("log2_block", C.c_int32), ("threshold", C.c_float), ("words", C.c_void_p), ("n_words", C.c_int64)]
+
+
+class CulledVolumeRenderArgs(C.Structure):
+    """nrnerf_culled_volume_render_args (ABI 10 additions): nrnerf_sh_volume_render_args' fields (sh NULL at degree 0), then the volume's
+    occupancy mask, the log2 of its block and its word count."""
+    _fields_ = ShVolumeRenderArgs._fields_ + [("occupancy", C.c_void_p), ("occupancy_log2_block", C.c_int32), ("occupancy_words", C.c_int64)]
+
+
+OCCUPANCY_MIN_LOG2_BLOCK, OCCUPANCY_MAX_LOG2_BLOCK = 1, 4
+
+
+def occupancy_blocks(g: int, log2_block: int) -> int:
+    """Blocks per axis of ``g`` vertices (``g - 1`` cells) at ``2 ** log2_block`` cells per block (include/nrnerf.h, "occupancy masks")."""
+    return (g - 1 + (1 << log2_block) - 1) >> log2_block
+
+
+def occupancy_words(g, log2_block: int) -> int:
+    """nrnerf_occupancy_words restated: the 32-bit words of the mask of a ``(gx, gy, gz)`` grid."""
+    n = 1
+    for v in g:
+        n *= occupancy_blocks(int(v), log2_block)
+    return (n + 31) // 32
+
+
 class GridLookupBackwardArgs(C.Structure):
     """nrnerf_grid_lookup_backward_args (ABI 10 additions): the adjoint of the grid lookup -- d grid (added into, float32) and d points from the
     cotangents of the looked-up values."""
@@ -471,6 +499,9 @@ EXPORTS = {
     "nrnerf_warped_volume_render": (C.c_int, [C.POINTER(WarpedVolumeRenderArgs), C.c_void_p]),
     "nrnerf_grid_lookup_backward": (C.c_int, [C.POINTER(GridLookupBackwardArgs), C.c_void_p]),
     "nrnerf_sh_volume_render": (C.c_int, [C.POINTER(ShVolumeRenderArgs), C.c_void_p]),
+    "nrnerf_occupancy_words": (C.c_int64, [C.POINTER(C.c_int32), C.c_int32]),
+    "nrnerf_occupancy_build": (C.c_int, [C.POINTER(OccupancyBuildArgs), C.c_void_p]),
+    "nrnerf_culled_volume_render": (C.c_int, [C.POINTER(CulledVolumeRenderArgs), C.c_void_p]),
     "nrnerf_bend_points_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "nrnerf_bend_points": (C.c_int, [C.c_void_p, C.POINTER(BendPointsArgs), C.c_void_p]),
     "nrnerf_generate_rays": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -93,6 +93,7 @@ struct GridFetch {
 };
 
 // where the point falls, and the requests for its eight corners (none for an empty sample)
+// (culled_grid_fetch of nrnerf_culled_volume.hip is this text with an occupancy bit in t.ok: a fix here belongs there too)
 template <bool HALF>
 __device__ __forceinline__ void grid_fetch(const GridArgs& a, const float px, const float py, const float pz, GridFetch<HALF>& t) {
     typedef typename GridFetch<HALF>::vertex vertex;

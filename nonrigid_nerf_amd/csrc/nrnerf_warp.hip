@@ -14,11 +14,15 @@
 // surface_index itself on the weights composite_ray returns, and lane 0 bends the one sample it picks again.
 // warped_lookup_kernel<VHALF, WHALF>: the same per-sample rule, one thread per sample, no compositing.
 // No multiply-add is fused that the rule does not name: every product that feeds a sum goes through rounded() (nrnerf_volume_lookup.h).
+// bend / removed / sample_bent live in nrnerf_baked_sample.h, shared with nrnerf_sh_volume.hip and nrnerf_culled_volume.hip.
+// A COPY of warped_render_kernel with an occupancy bit in the sample's flag is culled_render_kernel (nrnerf_culled_volume.hip; this object
+// must keep exactly its kernels): a fix here belongs there too.
 #include <hip/hip_runtime.h>
 
 #include "nrnerf_warp.h"
 #include "nrnerf_composite_ray.h"
 #include "nrnerf_volume_lookup.h"
+#include "nrnerf_baked_sample.h"
 
 namespace nrn {
 
@@ -26,36 +30,6 @@ namespace {
 
 constexpr int WARP_WAVES = 4;           // waves (= rays in flight) per workgroup
 constexpr int WARP_MAXS = 1024;         // NRNERF_MAX_SAMPLES: EPL <= 16
-
-// (u, m) at p -> (bent xyz, m after the cutoff): rnh:563-570
-__device__ __forceinline__ f32x4 bend(const WarpArgs& a, const float (&p)[3], const f32x4 um) {
-    float m = um[3];
-    if (a.has_cutoff && m <= a.cutoff) m = 0.0f;
-    f32x4 b;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float off = rounded(m * um[c]);
-        if (a.has_scaling) off = rounded(off * a.scaling);
-        b[c] = __fadd_rn(p[c], off);
-    }
-    b[3] = m;
-    return b;
-}
-
-// the removal knob on a sample's logits (a product: NaN stays NaN)
-__device__ __forceinline__ f32x4 removed(const WarpArgs& a, f32x4 r, const float m) {
-    if (a.has_removal && m >= a.removal) r[3] = rounded(r[3] * 0.0f);
-    return r;
-}
-
-// sample ic of `ray` in one go: (bent xyz, m)
-template <bool WHALF>
-__device__ __forceinline__ f32x4 sample_bent(const WarpArgs& a, const int ray, const int ic) {
-    const __attribute__((address_space(1))) float* rp = gmem(a.c.rays) + (size_t)ray * a.c.ray_stride;
-    float p[3];
-    sample_point(rp, sample_depth(a.c, rp, ray, ic), p);
-    return bend(a, p, volume_at<WHALF>(a.warp, p[0], p[1], p[2]));
-}
 
 template <int EPL, bool VHALF, bool WHALF>
 __global__ void __launch_bounds__(WARP_WAVES * 64) warped_render_kernel(const WarpArgs a) {

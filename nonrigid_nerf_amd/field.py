@@ -821,7 +821,7 @@ def sample_rays(rays, N_samples, lindisp=False):
 
 
 def render_volume(volume, rays, *, network=None, latents=None, N_samples=192, z_vals=None, lindisp=False, white_bkgd=False, surface=False,
-                  retraw=False, removal_threshold=None, precision=None):
+                  retraw=False, removal_threshold=None, precision=None, occupancy=None):
     """A baked volume rendered along ``rays [N, >= 8]``: ``rgb_map / disp_map / acc_map`` (+ ``raw`` under ``retraw``; ``surface_pts``,
     ``surface_rigidity``, ``median_index`` under ``surface``), no trunk pass.
 
@@ -832,7 +832,9 @@ def render_volume(volume, rays, *, network=None, latents=None, N_samples=192, z_
     background stabilisation included, from one bake.  Without ``network`` (or without a bender): straight rays, no bender launch -- a bake of
     one time step's observed space, or a static scene.  Refuses autograd inputs (``Unsupported``): a preview has no gradient.
     A volume record with ``"sh"`` (``bake(sh_degree=1 or 2)`` of a view-dependent head) goes through ``sh_volume_render`` instead: the colour
-    of a sample is evaluated at its direction -- the difference of consecutive bent points behind a bender, the ray's direction without."""
+    of a sample is evaluated at its direction -- the difference of consecutive bent points behind a bender, the ray's direction without.
+    ``occupancy``: the volume's mask (``build_occupancy``) -- samples in empty blocks request nothing, through ``culled_volume_render``; ``None``
+    takes the calls above."""
     if rays.device.type != "cuda":
         raise R.Unsupported("rays are not on a ROCm device")
     lat_t = latents if torch.is_tensor(latents) else None
@@ -881,7 +883,11 @@ def render_volume(volume, rays, *, network=None, latents=None, N_samples=192, z_
             removal_threshold = None
         if _has_sh(volume):         # a view-dependent bake: bent points give the directions by differences, straight rays their own
             return sh_volume_render(volume, rays, N_samples=S, z_vals=z, points4=points4, lindisp=lindisp, white_bkgd=white_bkgd,
-                                    removal_threshold=removal_threshold, retraw=retraw, surface=surface)
+                                    removal_threshold=removal_threshold, retraw=retraw, surface=surface, occupancy=occupancy)
+        if occupancy is not None:
+            return culled_volume_render(volume, rays, occupancy=occupancy, use_sh=False, N_samples=S, z_vals=z, points4=points4,
+                                        lindisp=lindisp, white_bkgd=white_bkgd, removal_threshold=removal_threshold, retraw=retraw,
+                                        surface=surface)
         return volume_render(volume, rays, N_samples=S, z_vals=z, points4=points4, lindisp=lindisp, white_bkgd=white_bkgd,
                              removal_threshold=removal_threshold, retraw=retraw, surface=surface)
 
@@ -889,7 +895,7 @@ def render_volume(volume, rays, *, network=None, latents=None, N_samples=192, z_
 def render_volume_frames(volume, render_poses, intrinsics, near, far, *, network=None, latents=None, **kwargs):
     """``render_volume`` for every camera of ``render_poses`` (``driver.generate_rays`` per frame): ``(rgbs uint8 [F, H, W, 3], disps float32
     [F, H, W])`` on the device, ``rgbs`` by the reference's truncating ``to8b`` (run_nerf_helpers.py:19).  ``latents``: one code per frame
-    ``[F, latent_size]``, or one code for all frames; ``kwargs``: ``render_volume``'s."""
+    ``[F, latent_size]``, or one code for all frames; ``kwargs``: ``render_volume``'s (``occupancy=`` among them: one mask serves every frame)."""
     from .driver import generate_rays
     dev = volume["raw"].device
     H, W = int(intrinsics["height"]), int(intrinsics["width"])
@@ -989,12 +995,19 @@ def bake_warps(render_kwargs_or_network, latents, min_point=None, max_point=None
 
 def warped_volume_render(volume, warp, rays, *, N_samples, z_vals=None, lindisp=False, white_bkgd=False, rigidity_cutoff=None,
                          test_time_scaling=None, removal_threshold=None, composite=True, retraw=False, weights=False, alpha=False,
-                         surface=False, return_points=False):
+                         surface=False, return_points=False, occupancy=None):
     """``nrnerf_warped_volume_render`` on tensors: the ``N_samples`` samples ``o + d z`` of every ray bent by ``warp`` (the knobs applied here),
     the canonical ``volume``'s logits at the bent points, and their compositing -- one kernel.  ``rays [N, >= 8]``; ``z_vals [N, S]`` or the
     coarse spacing between the rays' near and far.  Returns ``rgb_map / disp_map / acc_map`` (+ ``raw``, ``weights``, ``alpha``,
     ``surface_pts``, ``surface_rigidity``, ``median_index``, ``points4 [N, S, 4]`` = (bent xyz, rigidity after the cutoff) as asked for);
-    ``composite=False`` runs the lookup alone and returns ``raw`` and / or ``points4``.  The value rule: include/nrnerf.h."""
+    ``composite=False`` runs the lookup alone and returns ``raw`` and / or ``points4``.  The value rule: include/nrnerf.h.
+    ``occupancy``: the volume's mask (``build_occupancy``) -- the same call through ``culled_volume_render``, which requests nothing for a
+    sample in an empty block; ``None`` is this call."""
+    if occupancy is not None:
+        return culled_volume_render(volume, rays, occupancy=occupancy, use_sh=False, warp=warp, N_samples=N_samples, z_vals=z_vals,
+                                    lindisp=lindisp, white_bkgd=white_bkgd, rigidity_cutoff=rigidity_cutoff,
+                                    test_time_scaling=test_time_scaling, removal_threshold=removal_threshold, composite=composite,
+                                    retraw=retraw, weights=weights, alpha=alpha, surface=surface, return_points=return_points)
     vol, lo, hi, g = _grid_parts(volume, "raw", "volume")
     grid, wlo, whi, wg = _grid_parts(warp, "warp", "warp")
     dev = vol.device
@@ -1046,13 +1059,19 @@ def _sh_parts(volume, vol):
 
 def sh_volume_render(volume, rays, *, N_samples, warp=None, points4=None, z_vals=None, lindisp=False, white_bkgd=False, rigidity_cutoff=None,
                      test_time_scaling=None, removal_threshold=None, composite=True, retraw=False, weights=False, alpha=False,
-                     surface=False, return_points=False, ray_directions=None):
+                     surface=False, return_points=False, ray_directions=None, occupancy=None):
     """``nrnerf_sh_volume_render`` on tensors: ``warped_volume_render`` for a volume record with ``"sh"`` (``bake(sh_degree=1 or 2)``) -- per
     sample the colour logits are ``raw`` plus the spherical harmonics at the sample's direction times the coefficients at the bent point.
     The bent points are ``warp``'s (a ``bake_warp`` record; the knobs applied here), the ready-made ``points4 [N, S, 4]`` (not with a warp),
     or the straight samples.  ``ray_directions``: ``True`` takes every sample's direction from its ray, ``False`` from the difference of
     consecutive bent points (needs 2 samples or more); ``None`` picks differences whenever a warp or ``points4`` is given, as the reference
     does for a head behind a bender.  Outputs and the other arguments: ``warped_volume_render``'s.  The value rule: include/nrnerf.h."""
+    if occupancy is not None:
+        return culled_volume_render(volume, rays, occupancy=occupancy, use_sh=True, warp=warp, points4=points4, N_samples=N_samples,
+                                    z_vals=z_vals, lindisp=lindisp, white_bkgd=white_bkgd, rigidity_cutoff=rigidity_cutoff,
+                                    test_time_scaling=test_time_scaling, removal_threshold=removal_threshold, composite=composite,
+                                    retraw=retraw, weights=weights, alpha=alpha, surface=surface, return_points=return_points,
+                                    ray_directions=ray_directions)
     vol, lo, hi, g = _grid_parts(volume, "raw", "volume")
     sh, degree = _sh_parts(volume, vol)
     dev = vol.device
@@ -1100,15 +1119,132 @@ def sh_volume_render(volume, rays, *, N_samples, warp=None, points4=None, z_vals
     return out
 
 
+# --------------------------------------------------------------------------------------------
+# occupancy masks (nrnerf_occupancy_build / nrnerf_culled_volume_render): a baked render that skips empty space
+# --------------------------------------------------------------------------------------------
+def build_occupancy(volume, *, block=8, threshold=0.0):
+    """The occupancy mask of a baked volume: ``{"bits": int32 [words], "block", "grid": (Gz, Gy, Gx), "threshold"}`` -- one bit per block of
+    ``block`` (2, 4, 8 or 16) cells per axis, set iff some corner of some cell of the block has a sigma logit that is not ``<= threshold`` or
+    a ``raw`` channel that is not finite (the rule: include/nrnerf.h, "occupancy masks").  ``volume``: a ``bake`` record, with or without
+    ``"sh"``, or a bare grid ``[Gz, Gy, Gx, 4]`` on the device; an ``"sh"`` array must be finite (``ValueError``).
+    ``threshold=0`` is exact: every map ``render_baked(..., occupancy=mask)`` returns keeps the bits of the unmasked render.  ``threshold >
+    0`` also drops blocks of thin density: lossy.  A negative threshold is a ``ValueError``.
+    A mask is a SNAPSHOT: after ``refine_bake`` (or anything else) changes the volume, build it again -- a stale mask is not detected."""
+    block = int(block)
+    if block not in (2, 4, 8, 16):
+        raise ValueError(f"an occupancy block is 2, 4, 8 or 16 cells per axis, got {block}")
+    threshold = float(threshold)
+    if not threshold >= 0.0:
+        raise ValueError(f"an occupancy threshold is >= 0 (0: exact), got {threshold}")
+    record = volume if isinstance(volume, dict) else {"raw": volume, "min_point": (0.0, 0.0, 0.0), "max_point": (1.0, 1.0, 1.0)}
+    vol, _, _, g = _grid_parts(record, "raw", "volume")
+    if _has_sh(record):
+        sh, _ = _sh_parts(record, vol)
+        if not bool(torch.isfinite(sh).all()):
+            raise ValueError("the sh array holds a value that is not finite: no mask can vouch for a render of it")
+    k = block.bit_length() - 1
+    dev = vol.device
+    bits = torch.empty((_lib.occupancy_words(g, k),), dtype=torch.int32, device=dev)
+    a = _lib.OccupancyBuildArgs()
+    a.struct_size = C.sizeof(a)
+    a.volume, a.volume_dtype = vol.data_ptr(), _VOLUME_DTYPES[vol.dtype]
+    a.g[:] = g
+    a.log2_block, a.threshold = k, threshold
+    a.words, a.n_words = bits.data_ptr(), int(bits.numel())
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().nrnerf_occupancy_build(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "nrnerf_occupancy_build")
+    return {"bits": bits, "block": block, "grid": (g[2], g[1], g[0]), "threshold": threshold}
+
+
+def _occupancy_parts(occupancy, vol, g):
+    """A ``build_occupancy`` record checked against the volume it is used with: ``(bits contiguous, log2 of the block)``."""
+    block = int(occupancy["block"])
+    if block not in (2, 4, 8, 16):
+        raise ValueError(f"an occupancy block is 2, 4, 8 or 16 cells per axis, got {block}")
+    if tuple(int(v) for v in occupancy["grid"]) != (g[2], g[1], g[0]):
+        raise ValueError(f"the occupancy mask was built for a grid {tuple(occupancy['grid'])}, the volume is {(g[2], g[1], g[0])}")
+    bits = occupancy["bits"]
+    k = block.bit_length() - 1
+    if not torch.is_tensor(bits) or bits.device != vol.device:
+        raise R.Unsupported("the occupancy mask is not on the volume's device")
+    if bits.dtype != torch.int32 or bits.dim() != 1 or int(bits.numel()) != _lib.occupancy_words(g, k):
+        raise ValueError(f"the occupancy mask of this volume is int32 [{_lib.occupancy_words(g, k)}], got {bits.dtype} {tuple(bits.shape)}")
+    return bits.contiguous(), k
+
+
+def culled_volume_render(volume, rays, *, occupancy, N_samples, use_sh=None, warp=None, points4=None, z_vals=None, lindisp=False,
+                         white_bkgd=False, rigidity_cutoff=None, test_time_scaling=None, removal_threshold=None, composite=True, retraw=False,
+                         weights=False, alpha=False, surface=False, return_points=False, ray_directions=None):
+    """``nrnerf_culled_volume_render`` on tensors: ``sh_volume_render`` -- or, for a record without ``"sh"`` (and with ``use_sh=False``),
+    ``warped_volume_render`` / ``volume_render`` -- with the volume's ``occupancy`` mask (``build_occupancy``): a sample whose bent point falls
+    in an empty block is an empty sample and requests nothing.  The bent points are ``warp``'s, the ready-made ``points4``, or the straight
+    samples.  Arguments and outputs: ``sh_volume_render``'s.  The mask must have been built from this volume as it is now (a snapshot: rebuild
+    it after ``refine_bake``); only its grid shape is checked (``ValueError``)."""
+    vol, lo, hi, g = _grid_parts(volume, "raw", "volume")
+    if use_sh is None:
+        use_sh = _has_sh(volume)
+    sh, degree = _sh_parts(volume, vol) if use_sh else (None, 0)
+    bits, k = _occupancy_parts(occupancy, vol, g)
+    dev = vol.device
+    if warp is not None and points4 is not None:
+        raise ValueError("a warp bends the samples itself: points4 cannot be given with it")
+    a = _lib.CulledVolumeRenderArgs()
+    N, S, keep = _render_front(a, dev, rays, N_samples, z_vals, lindisp, white_bkgd)
+    a.volume, a.volume_dtype = vol.data_ptr(), _VOLUME_DTYPES[vol.dtype]
+    a.g[:] = g
+    a.min_point[:], a.max_point[:] = lo.tolist(), hi.tolist()
+    if sh is not None:
+        a.sh = sh.data_ptr()
+    a.sh_degree = degree
+    a.occupancy, a.occupancy_log2_block, a.occupancy_words = bits.data_ptr(), k, int(bits.numel())
+    if warp is not None:
+        grid, wlo, whi, wg = _grid_parts(warp, "warp", "warp")
+        if grid.device != dev:
+            raise ValueError(f"the volume is on {dev}, the warp on {grid.device}")
+        a.warp, a.warp_dtype = grid.data_ptr(), _VOLUME_DTYPES[grid.dtype]
+        a.warp_g[:] = wg
+        a.warp_min_point[:], a.warp_max_point[:] = wlo.tolist(), whi.tolist()
+    elif rigidity_cutoff is not None or test_time_scaling is not None:
+        raise ValueError("the rigidity cutoff and the scaling act on a warp")
+    if points4 is not None:
+        if tuple(points4.shape) != (N, S, 4):
+            raise ValueError(f"points4 must be {(N, S, 4)}, got {tuple(points4.shape)}")
+        points4 = points4.detach().to(dtype=torch.float32, device=dev).contiguous()
+        a.points4_in = points4.data_ptr() or None
+    if ray_directions is None:
+        ray_directions = warp is None and points4 is None
+    if degree and not ray_directions and S < 2:
+        raise ValueError("a direction from the difference of bent points needs 2 samples or more")
+    a.direction_mode = _lib.SH_DIRECTION_RAY if ray_directions else _lib.SH_DIRECTION_DIFFERENCES
+    if rigidity_cutoff is not None:
+        a.has_rigidity_cutoff, a.rigidity_cutoff = 1, float(rigidity_cutoff)
+    if test_time_scaling is not None:
+        a.has_test_time_scaling, a.test_time_scaling = 1, float(test_time_scaling)
+    if removal_threshold is not None:
+        a.has_removal_threshold, a.removal_threshold = 1, float(removal_threshold)
+    out, new = _render_outputs(a, dev, N, S, composite, weights, alpha, surface)
+    if retraw or (not composite and not return_points):
+        a.raw = new("raw", N, S, 4)
+    if return_points:
+        a.points4 = new("points4", N, S, 4)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().nrnerf_culled_volume_render(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "nrnerf_culled_volume_render")
+    return out
+
+
 def render_baked(volume, warp, rays, *, N_samples=192, z_vals=None, lindisp=False, white_bkgd=False, rigidity_cutoff=None,
-                 test_time_scaling=None, removal_threshold=None, surface=False, retraw=False, return_points=False):
+                 test_time_scaling=None, removal_threshold=None, surface=False, retraw=False, return_points=False, occupancy=None):
     """A baked scene rendered along ``rays [N, >= 8]`` with no network, no model handle and no latent code: ``volume`` is the canonical ``bake``,
     ``warp`` the ``bake_warp`` of the time step.  ``rgb_map / disp_map / acc_map`` (+ ``raw`` under ``retraw``; ``surface_pts``,
     ``surface_rigidity``, ``median_index`` under ``surface``; ``points4`` under ``return_points``).  The samples are ``N_samples`` of the coarse
     spacing (``lindisp`` honoured) or ``z_vals [N, S]``.  ``rigidity_cutoff`` (background stabilisation), ``test_time_scaling`` (motion
     exaggeration) and ``removal_threshold`` are the bender's test-time knobs, applied per sample at render time; ``None`` is off.  Refuses
     autograd inputs (``Unsupported``): a preview has no gradient.  A volume record with ``"sh"`` (a view-dependent bake) goes through
-    ``sh_volume_render``: the colour of a sample is evaluated at the difference of the ray's consecutive bent points."""
+    ``sh_volume_render``: the colour of a sample is evaluated at the difference of the ray's consecutive bent points.
+    ``occupancy``: the volume's mask (``build_occupancy(volume)``): samples whose bent point falls in an empty block request nothing.  At the
+    mask's ``threshold=0`` every map keeps its bits; ``raw`` is zero at the skipped samples.  ``None`` takes the unmasked kernels."""
     if not torch.is_tensor(rays) or rays.device.type != "cuda":
         raise R.Unsupported("rays are not on a ROCm device")
     if torch.is_grad_enabled() and (rays.requires_grad or volume["raw"].requires_grad or warp["warp"].requires_grad
@@ -1120,17 +1256,17 @@ def render_baked(volume, warp, rays, *, N_samples=192, z_vals=None, lindisp=Fals
         if _has_sh(volume):         # a view-dependent bake: the same kernel with a colour per direction (differences of the bent points)
             return sh_volume_render(volume, rays, warp=warp, N_samples=S, z_vals=z, lindisp=lindisp, white_bkgd=white_bkgd,
                                     rigidity_cutoff=rigidity_cutoff, test_time_scaling=test_time_scaling, removal_threshold=removal_threshold,
-                                    retraw=retraw, surface=surface, return_points=return_points)
+                                    retraw=retraw, surface=surface, return_points=return_points, occupancy=occupancy)
         return warped_volume_render(volume, warp, rays, N_samples=S, z_vals=z, lindisp=lindisp, white_bkgd=white_bkgd,
                                     rigidity_cutoff=rigidity_cutoff, test_time_scaling=test_time_scaling, removal_threshold=removal_threshold,
-                                    retraw=retraw, surface=surface, return_points=return_points)
+                                    retraw=retraw, surface=surface, return_points=return_points, occupancy=occupancy)
 
 
 def render_baked_frames(volume, warps, render_poses, intrinsics, near, far, **kwargs):
     """``render_baked`` for every camera of ``render_poses`` (``driver.generate_rays`` per frame): ``(rgbs uint8 [F, H, W, 3], disps float32
     [F, H, W])`` on the device, ``rgbs`` by the reference's truncating ``to8b`` (run_nerf_helpers.py:19).  ``warps``: what ``bake_warps``
     returns (``[F, Gz, Gy, Gx, 4]``, one grid per frame; ``[1, ...]`` or what ``bake_warp`` returns: one grid for all frames); ``kwargs``:
-    ``render_baked``'s."""
+    ``render_baked``'s (``occupancy=`` among them: the mask is the canonical volume's, one serves every frame)."""
     from .driver import generate_rays
     dev = volume["raw"].device
     H, W = int(intrinsics["height"]), int(intrinsics["width"])
