@@ -198,7 +198,13 @@ typedef enum nrnerf_render_flags {
      * finished the previous one.  (Measured: the two workgroups of a CU do not run the bender at the same rate, and the eight XCDs do not
      * run the trunk at the same rate -- 3.7 % between the fastest and the slowest --, so with fixed shares a launch ends with idle CUs.)
      * Same bits either way: which wave evaluates a sample does not enter the arithmetic. */
-    NRNERF_RENDER_FIXED_SHARES = 1u << 8
+    NRNERF_RENDER_FIXED_SHARES = 1u << 8,
+    /* The 16x16x32 trunk kernel WITHOUT its resident slice.  By default a launch of that kernel on the 256-wide plain-headed trunk keeps the
+     * first layer's, the skip layer's encoding and the head's weight fragments (72 KiB) in LDS and streams only the seven 256 x 256 blocks
+     * through the ring -- wherever that fits the 160 KiB of LDS (not: 256 fused samples per ray, sample counts whose fused stage holds four
+     * rays per wave, the coarse epilogue).  This bit keeps the kernel that streams the whole image every iteration (A/B and bit-identity
+     * tests).  Same bits either way: where a weight fragment is read from does not enter the arithmetic.  nrnerf_query always takes the default. */
+    NRNERF_RENDER_NO_RESIDENT_SLICE = 1u << 9
 } nrnerf_render_flags;
 
 /* per-kernel device time accumulated between nrnerf_profile_begin/_end (HIP events on the render stream) */
@@ -782,6 +788,14 @@ int nrnerf_composite_backward(const nrnerf_composite_args* args, void* hip_strea
 
 /* profiling: records hipEvents around each kernel of subsequent nrnerf_render calls on this model */
 int nrnerf_profile_begin(nrnerf_model* model);
+/* Launches of the 16x16x32 trunk kernel's resident-slice variant (NRNERF_RENDER_NO_RESIDENT_SLICE) per profile slot -- 0: coarse network,
+ * 2: fine network, the others stay 0 -- since the last nrnerf_profile_begin (or the handle's creation); counted whether or not a profile is
+ * being recorded.  The profile's display names do not say which variant ran; this does. */
+int nrnerf_resident_launches(const nrnerf_model* model, int32_t out[6]);
+/* Host-only: the LDS bytes a launch of the 16x16x32 trunk kernel (256-wide, plain head; precision NRNERF_PREC_BF16 / _F16) requests for a pass of
+ * n_samples per ray -- fused: with the compositing as its epilogue; resident: the resident-slice variant.  A launch takes that variant when
+ * its request is at most 160 KiB.  0: no such kernel. */
+size_t nrnerf_trunk_kernel_lds_bytes(int32_t precision, int32_t n_samples, int32_t fused, int32_t resident);
 int nrnerf_profile_end(nrnerf_model* model, nrnerf_profile* out);   /* synchronises the recorded events */
 
 /* ABI 9: the images free_viewpoint_rendering.py (fvr) writes for every frame, computed on the device from what a render already holds
@@ -1394,6 +1408,9 @@ int nrnerf_culled_volume_render(const nrnerf_culled_volume_render_args* args, vo
  *   architecture, nrnerf_generic_trunk_backward): transposed layers in reverse order; the unit table holds n_layers, per layer the 11
  *   integers of 7 / 8 plus {save slot, mask slot, column offsets of the two sources in the hidden buffer} (dst 4 / 5 / 6: straight to
  *   d_enc0 / d_enc1 / d_encv), then the three padded widths, the latent size and the hidden-buffer column where the rows of d raw start.
+ * 15 = no image: the RESIDENT-SLICE table of image 10 (plain head, width 256 only) as the 16x16x32 kernel reads it.  The unit table holds
+ *   n_resident, the image fragment of every slot of the resident LDS block, n_ring_units, fragments per unit, then per ring unit its offset in
+ *   the image in 16-byte words (n_units = that many entries minus one); stream_bytes is 0.
  * Any output pointer may be NULL to query sizes only.  Used by the CPU-side packing tests. */
 typedef struct nrnerf_packed_info {
     uint64_t stream_bytes;     /* fragment stream */

@@ -89,7 +89,7 @@ MODEL_FORCE_GENERIC, MODEL_NO_X16_F16 = 1 << 0, 1 << 1
 # described to the library without exact_viewdirs, which the run-time-parameterised RENDER kernel does not do (training.render_rays_train)
 MODEL_PY_TRAINING_HANDLE = 1 << 30
 RENDER_FUSED_FINE_BENDER, RENDER_UNFUSED_COMPOSITE, RENDER_SPLIT_COARSE, RENDER_NO_X16, RENDER_X16_FINE_ONLY, RENDER_BENDER_32X32, \
-    RENDER_COARSE_EPILOGUE_ON, RENDER_COARSE_EPILOGUE_OFF, RENDER_FIXED_SHARES = (1 << i for i in range(9))
+    RENDER_COARSE_EPILOGUE_ON, RENDER_COARSE_EPILOGUE_OFF, RENDER_FIXED_SHARES, RENDER_NO_RESIDENT_SLICE = (1 << i for i in range(10))
 
 
 def model_flags_from_env() -> int:
@@ -103,13 +103,13 @@ def model_flags_from_env() -> int:
 
 
 _RENDER_ENV = ("NRNERF_FUSED_FINE_BENDER", "NRNERF_UNFUSED_COMPOSITE", "NRNERF_SPLIT_COARSE", "NRNERF_X16_BENDER", "NRNERF_X16",
-               "NRNERF_FUSED_COARSE_EPILOGUE", "NRNERF_FIXED_SHARES")
+               "NRNERF_FUSED_COARSE_EPILOGUE", "NRNERF_FIXED_SHARES", "NRNERF_RESIDENT_SLICE")
 _render_flags_cache = (None, 0)
 
 
 def render_flags_from_env() -> int:
     """NRNERF_FUSED_FINE_BENDER=1, NRNERF_UNFUSED_COMPOSITE=1, NRNERF_SPLIT_COARSE=1, NRNERF_X16=0|1|2, NRNERF_X16_BENDER=0,
-    NRNERF_FUSED_COARSE_EPILOGUE=0|1 -> nrnerf_render_args.flags (read per call: the parity tests render one scene through several kernel
+    NRNERF_FUSED_COARSE_EPILOGUE=0|1, NRNERF_FIXED_SHARES=1, NRNERF_RESIDENT_SLICE=0 -> nrnerf_render_args.flags (read per call: the parity tests render one scene through several kernel
     routes in one process; parsed once per distinct set of values -- a small-batch render should not pay for six string comparisons)."""
     global _render_flags_cache
     key = tuple(os.environ.get(k) for k in _RENDER_ENV)
@@ -135,6 +135,8 @@ def render_flags_from_env() -> int:
         f |= RENDER_COARSE_EPILOGUE_ON if key[5].strip() == "1" else RENDER_COARSE_EPILOGUE_OFF
     if key[6] == "1":
         f |= RENDER_FIXED_SHARES
+    if key[7] == "0":
+        f |= RENDER_NO_RESIDENT_SLICE
     _render_flags_cache = (key, f)
     return f
 
@@ -526,6 +528,8 @@ EXPORTS = {
     "nrnerf_composite_forward": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
     "nrnerf_composite_backward": (C.c_int, [C.POINTER(CompositeArgs), C.c_void_p]),
     "nrnerf_profile_begin": (C.c_int, [C.c_void_p]),
+    "nrnerf_resident_launches": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "nrnerf_trunk_kernel_lds_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "nrnerf_profile_end": (C.c_int, [C.c_void_p, C.POINTER(Profile)]),
     "nrnerf_visualize_frames": (C.c_int, [C.POINTER(VisualizeArgs), C.c_void_p]),
     "nrnerf_visualize_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

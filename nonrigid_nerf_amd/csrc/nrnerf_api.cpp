@@ -525,6 +525,11 @@ struct RenderCall {
             return timed(ev, [&] {
                 if (p.net != NetFamily::NetX16) return launch_net(m->precision, p.net == NetFamily::NetBender, m->views, p.dispatch, n, m->num_cus, stream);
                 n.work_counter = counter(p.trunk_counter, (size_t)16 * BEND_COUNTERS_PER_LAUNCH * 2 + 16 * p.which);
+                n.no_resident = (a->flags & NRNERF_RENDER_NO_RESIDENT_SLICE) ? 1 : 0;
+                if (x16_takes_resident(m->precision, p.dispatch, m->views, n)) {      // (the launcher's own rule; the display name stays)
+                    std::lock_guard<std::mutex> g(m->prof_mu);
+                    ++m->resident_launches[p.net_slot];
+                }
                 return launch_net_x16(m->precision, p.dispatch, m->views, n, m->num_cus, stream);
             });
         }
@@ -838,9 +843,23 @@ int nrnerf_profile_begin(nrnerf_model* m) try {
     std::lock_guard<std::mutex> g(m->prof_mu);
     for (auto& e : m->prof_events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     m->prof_events.clear();
+    for (int& n : m->resident_launches) n = 0;
     m->prof_on = true;
     return NRNERF_OK;
 } NRN_CATCH
+
+int nrnerf_resident_launches(const nrnerf_model* m, int32_t out[6]) try {
+    if (!m || !out) return NRNERF_ERR_INVALID;
+    std::lock_guard<std::mutex> g(m->prof_mu);
+    for (int i = 0; i < NRNERF_NUM_KERNELS; ++i) out[i] = m->resident_launches[i];
+    return NRNERF_OK;
+} NRN_CATCH
+
+size_t nrnerf_trunk_kernel_lds_bytes(int32_t precision, int32_t n_samples, int32_t fused, int32_t resident) {
+    const int prec = precision == NRNERF_PREC_BF16 ? PREC_BF16 : (precision == NRNERF_PREC_F16 ? PREC_F16 : -1);
+    if (prec < 0 || n_samples < 1 || n_samples > NRNERF_MAX_SAMPLES) return 0;
+    return x16_lds_request(prec, 0, false, n_samples, fused != 0, false, resident != 0);
+}
 
 int nrnerf_profile_end(nrnerf_model* m, nrnerf_profile* out) try {
     if (!m || !out) return NRNERF_ERR_INVALID;

@@ -103,6 +103,9 @@ struct NetArgs {
     // compositing) / of blocks from it as they finish the previous one, instead of every gridDim-th one (round 6: the eight XCDs run the
     // kernel at rates 3.7 % apart, and with fixed shares the launch lasted as long as the slowest one's)
     unsigned* work_counter;
+    // net_kernel_x16 only: 1 = never the resident-slice variant (nrnerf_net_x16.h: the first layer's, the skip layer's encoding and the head's weights
+    // held in LDS, the ring streaming the 256 x 256 blocks alone), which a launch takes by default wherever it exists and its LDS request fits
+    int no_resident;
 };
 
 

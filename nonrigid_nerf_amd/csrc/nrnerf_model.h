@@ -76,6 +76,7 @@ struct nrnerf_model : nrn::ModelTraits {
     // profiling (guarded; the render path itself is otherwise read-only on the handle)
     mutable std::mutex prof_mu;
     mutable bool prof_on = false;
+    mutable int resident_launches[NRNERF_NUM_KERNELS] = {};      // net_kernel_x16's resident-slice variant, per profile slot, since profile_begin (prof_mu)
     struct Ev { int kernel; hipEvent_t a, b; double flops, mfma; const char* name; };
     mutable std::vector<Ev> prof_events;
 };

@@ -154,7 +154,9 @@ __device__ __forceinline__ void wait_ring() {
     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-template <class P, int WAVES, int NUP>
+// SRC: where unit V starts in the image -- void: at V * UNIT (the stream IS the image); else SRC::unit_src_bytes(V), a compile-time table
+// (the resident-slice ring below, whose units are runs of the image with resident fragments left out between them)
+template <class P, int WAVES, int NUP, class SRC = void>
 struct WRing {
     static constexpr int UNIT = P::UNIT_BYTES;
     // (Tried and rejected on MI355X: letting only 2 or 4 "loader" waves issue the DMA so their SIMD partners keep the
@@ -189,7 +191,9 @@ struct WRing {
         // hoisting one 64-bit per-lane address per unit out of the persistent loop (spilled VGPR pairs, and every scratch
         // reload drains the DMA queue with a vmcnt(0)).  The pieces of a wave are 1 KiB apart in the stream and in the
         // slot, which is what the instruction's immediate offset (added to the global and to the LDS address) expresses.
-        unsigned off = (unsigned)(V * UNIT);
+        unsigned off;
+        if constexpr (std::is_void<SRC>::value) off = (unsigned)(V * UNIT);
+        else off = (unsigned)SRC::unit_src_bytes(V);
         asm volatile("" : "+s"(off));
         const char* src = (ubase + off) + lane16;
         char* dst = ring + (V % RING) * UNIT + wave_off;
@@ -224,6 +228,11 @@ struct WRing {
     static constexpr bool ASM_FRAGS = (P::FRAG_BYTES == 1024);
     template <class PX, int GF>
     __device__ __forceinline__ typename PX::frag frag() {
+        return ring_frag<PX, GF>();
+    }
+    // ... by its index GF among the fragments the RING carries (frag: all of them)
+    template <class PX, int GF>
+    __device__ __forceinline__ typename PX::frag ring_frag() {
         static_assert(PX::FRAG_BYTES == P::FRAG_BYTES, "mixed policies must share the fragment size");
         constexpr int UF = P::UNIT_FRAGS;
         if constexpr (GF % UF == 0) advance<GF / UF>();
@@ -249,6 +258,73 @@ struct WRing {
         }
     }
     __device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+};
+
+// ------------------------------------------------------------------------------------------
+// The ring with a RESIDENT SLICE (RS = ResX16<..>, nrnerf_plan.h): the image's few fragments that do not belong to a W x W block are
+// copied to an LDS block of their own once per workgroup (init), the ring carries only RS::NUNITS whole units per pass -- a multiple of
+// RING, so there are no padding units.  frag<GF> (GF: index in the IMAGE, as the plain ring's) reads a resident fragment from the block
+// and a streamed one from the ring, both with the same asm ds_read_b128 in the same in-order LDS queue: the consumer's counted lgkmcnt
+// waits (dense_x16) see the same number of reads between a fragment and its use, whichever place each comes from.
+//
+// What the plain ring's arguments rest on, re-derived with resident fragments between the ring's:
+//  * slot reuse (LAG = 2).  advance<U> runs at the load of ring fragment 16 U, position j of the kernel's flat fragment sequence.  The
+//    consumer loads position j only after its counted wait for position j - PF (or, at a layer's start, after the previous layer's last
+//    wait, which drains everything): all reads at positions <= j - PF have RETIRED.  Unit U - 2's fragments are ring fragments
+//    < 16 (U - 1), at positions <= j - 17 -- resident fragments in between only move them further back -- and PF < 16.  So a wave at
+//    barrier U has retired its reads of unit U - 2, whose slot the DMA of unit U + 2 behind the barrier overwrites.  Across the
+//    iteration boundary (advance<0>, now at the first hidden layer's start: U + 2 = 2 goes where unit NUNITS - 2 was) the same holds:
+//    that unit was read a layer and a half earlier.  Between advance<NUNITS - 1> and the next advance<0> there is no barrier (head,
+//    outputs, compositing, encoding, first layer): the waves may drift apart there, but nothing is recycled without a barrier.
+//  * the counted vmcnt waits.  advance<U> waits until at most PW vector-memory operations of this wave are outstanding.  The queue
+//    retires in order and unit U's pieces are older than unit U + 1's PW pieces, so they have landed whatever else is in flight: the
+//    resident block's pieces (init: all waited for before the loop), the point loads, the counter atomic and the output stores (all
+//    behind advance<NUNITS - 1>'s requests, where they were behind the last padding unit's) can only make the wait stricter.
+// ------------------------------------------------------------------------------------------
+template <class P, int WAVES, class RS>
+struct WRingRes : WRing<P, WAVES, RS::NUNITS, RS> {
+    using Base = WRing<P, WAVES, RS::NUNITS, RS>;
+    static constexpr bool RESIDENT = true;
+    static constexpr int SPAN = 65536 / P::FRAG_BYTES;        // resident slots one base register reaches (16-bit immediate offset)
+    static constexpr int NBASE = (RS::NRES + SPAN - 1) / SPAN;
+    static_assert(Base::ASM_FRAGS && RS::NRES % WAVES == 0, "16-byte asm fragment reads; the block splits evenly over the waves");
+    unsigned res_addr[NBASE];      // LDS byte address of this lane's part of resident slot SPAN * i
+
+    template <int G> static constexpr bool is_resident() { return RS::resident(G); }
+    // `block`: RS::BYTES of LDS outside the ring.  Every wave copies piece `wave` of every run of WAVES resident slots (consecutive in
+    // the image: checked), by the ring's own LDS-DMA; the copy is complete -- vmcnt(0), then the workgroup barrier -- before init returns.
+    __device__ __forceinline__ void init(const void* stream, char* lds, char* block, int wave, int lane) {
+        Base::init(stream, lds, wave, lane);
+        const char* const src0 = (const char*)stream + wave * P::FRAG_BYTES + this->lane16;
+        char* const dst0 = block + wave * P::FRAG_BYTES;
+        static_for<0, RS::NRES / WAVES>([&](auto cc) {
+            constexpr int c = decltype(cc)::value;
+            static_assert(RS::T.res_src[c * WAVES + WAVES - 1] == RS::T.res_src[c * WAVES] + WAVES - 1, "a run of WAVES resident slots is contiguous in the image");
+            unsigned off = (unsigned)(RS::T.res_src[c * WAVES] * P::FRAG_BYTES);
+            asm volatile("" : "+s"(off));
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src0 + off),
+                                             (__attribute__((address_space(3))) void*)(dst0 + c * WAVES * P::FRAG_BYTES), 16, 0, 0);
+        });
+        static_for<0, NBASE>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            res_addr[i] = (unsigned)(size_t)(__attribute__((address_space(3))) char*)block + (unsigned)this->lane_off + (unsigned)(i * SPAN * P::FRAG_BYTES);
+            asm volatile("" : "+v"(res_addr[i]));      // (opaque, as bias_lane: one register per base instead of one per fragment address)
+        });
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    template <class PX, int GF>
+    __device__ __forceinline__ typename PX::frag frag() {
+        if constexpr (RS::resident(GF)) {
+            static_assert(PX::FRAG_BYTES == P::FRAG_BYTES, "mixed policies must share the fragment size");
+            constexpr int R = RS::T.res_of[GF];
+            u32x4 v;
+            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(res_addr[R / SPAN]), "n"((R % SPAN) * P::FRAG_BYTES));
+            return __builtin_bit_cast(typename PX::frag, v);
+        } else {
+            return Base::template ring_frag<PX, RS::T.ring_of[GF]>();
+        }
+    }
 };
 
 // ------------------------------------------------------------------------------------------

@@ -41,6 +41,10 @@ __device__ __forceinline__ typename P::frag x16_pack(const f32x4& d0, const f32x
     return __builtin_bit_cast(typename P::frag, w);
 }
 
+// a fragment source with a resident slice (WRingRes, nrnerf_net_impl.h)
+template <class ST, class = void> struct x16_has_resident : std::false_type {};
+template <class ST> struct x16_has_resident<ST, typename std::enable_if<ST::RESIDENT>::type> : std::true_type {};
+
 #ifndef NRN_X16_NB
 #define NRN_X16_NB 4          // 16-sample blocks per wave
 #endif
@@ -95,6 +99,9 @@ __device__ __forceinline__ void dense_x16(ST& st, const __attribute__((address_s
             asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(bias_addr), "n"((spec.tile0 + SQ::tile(q)) * 64));
             bias[SQ::tile(q)] = __builtin_bit_cast(f32x4, v);
         }
+        // (a ring with a resident slice: its table and this layer's own (tile, k-step) order agree on which fragments are resident)
+        if constexpr (x16_has_resident<ST>::value) static_assert(ST::template is_resident<G0 + q>() == (spec.kind == LK_TR_IN || spec.kind == LK_HEAD || (spec.kind == LK_TR_SKIP && s < NS0)),
+                                                  "resident-slice table and SeqPos disagree");
         if constexpr (s < NS0) a[q % PF] = __builtin_bit_cast(typename P1::frag, st.template frag<P0, G0 + q>());
         else a[q % PF] = st.template frag<P1, G0 + q>();
     };
@@ -160,9 +167,17 @@ __device__ __forceinline__ void dense_x16(ST& st, const __attribute__((address_s
 // SAMPLE (EPL > 0): the pass is the COARSE one of a hierarchical render -- behind composite_ray the wave also draws its ray's importance
 // depths, z_std and the merge (sample_merge_ray, nrnerf_composite_ray.h: composite_kernel<EPL, true>'s own code) from a private LDS area,
 // i.e. K1 of nrnerf_render's sequence becomes this kernel's epilogue and the coarse raw array never reaches HBM (train.py:889-920).
-template <class P, class A, int WAVES, int EPL, bool VIEWS = false, bool SAMPLE = false>
+// RES: the resident-slice variant (WRingRes, nrnerf_net_impl.h; ResX16, nrnerf_plan.h) of the plain-headed 256-wide trunk: the first layer's,
+// the skip layer's encoding k-steps' and the head's weight fragments (72 KiB) are copied to LDS once per workgroup and the ring streams the
+// seven 256 x 256 blocks alone -- 56 units per iteration instead of 64 (of which 3.5 were padding), 12.5 % fewer L2 -> LDS pieces and ring
+// barriers for the same MFMAs in the same order: the kernel is power-bound, and what it does not move it can spend on the matrix pipe
+// (DESIGN.md section 3.1d).  Same bits: only where a fragment is read from changes.  The launcher takes it when its LDS request fits.
+template <class A, bool VIEWS, bool SAMPLE> struct X16Res { static constexpr bool OK = !VIEWS && !SAMPLE && A::W == 256; };
+template <class P, class A, int WAVES, int EPL, bool VIEWS = false, bool SAMPLE = false, bool RES = false>
 __global__ void __launch_bounds__(WAVES * 64, 1) net_kernel_x16(const NetArgs a) {
     using PL = PlanX16<P, A, VIEWS>;
+    using RS = ResX16<P, A>;                                          // (only named unless RES)
+    static_assert(!RES || X16Res<A, VIEWS, SAMPLE>::OK, "the resident slice: plain head, no coarse epilogue, the 256-wide trunk");
     using PE = PolF16;                                                // the encoding's operands are f16 in both modes
     using frag = typename P::frag;
     using efrag = typename PE::frag;
@@ -175,7 +190,12 @@ __global__ void __launch_bounds__(WAVES * 64, 1) net_kernel_x16(const NetArgs a)
 #endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ring = smem;
-    float* bias_lds = (float*)(smem + RING * P::UNIT_BYTES);
+    size_t res_bytes = 0;                                             // (RES) the resident block sits between the ring and the bias table
+    if constexpr (RES) {
+        static_assert(RS::NRES == 72 && RS::NRING == 896 && RS::NUNITS == 56 && RS::NUNITS % RING == 0, "7 x 128 ring fragments = 56 units; 32 + 32 + 8 resident");
+        res_bytes = RS::BYTES;
+    }
+    float* bias_lds = (float*)(smem + RING * P::UNIT_BYTES + res_bytes);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 4, n = lane & 15;
@@ -184,8 +204,10 @@ __global__ void __launch_bounds__(WAVES * 64, 1) net_kernel_x16(const NetArgs a)
     __syncthreads();
     const __attribute__((address_space(3))) f32x4* bias_lane = (const __attribute__((address_space(3))) f32x4*)(bias_lds + 4 * g);
     asm volatile("" : "+v"(bias_lane));
-    WRing<P, WAVES, PL::NUP> st;
-    st.init(a.wstream, ring, wave, lane);
+    // (RES: the resident block is copied and waited for here -- once per workgroup, before the persistent loop and the first ring barrier)
+    typename std::conditional<RES, WRingRes<P, WAVES, RS>, WRing<P, WAVES, PL::NUP>>::type st;
+    if constexpr (RES) st.init(a.wstream, ring, smem + RING * P::UNIT_BYTES, wave, lane);
+    else st.init(a.wstream, ring, wave, lane);
 
     const int S = a.S;
     const int bpr = (S + 15) >> 4;
@@ -410,8 +432,10 @@ __global__ void __launch_bounds__(WAVES * 64, 1) net_kernel_x16(const NetArgs a)
         NRN_TACC(2, t_net);
         const unsigned long long t_out = NRN_NOW();
 #endif
-        // the stream's padding units: the ring runs on into the next iteration's first units
-        static_for<PL::NUNITS, PL::NUP>([&](auto uc) { st.template advance<decltype(uc)::value>(); });
+        // the stream's padding units: the ring runs on into the next iteration's first units.  (RES: there are none -- the iteration's last
+        // DMA requests are advance<55>'s, inside the last hidden layer; the head reads the resident block.  The point loads, the counter's
+        // atomic and the mailbox publish below stay where they are: behind the head, ahead of the output stores.)
+        if constexpr (!RES) static_for<PL::NUNITS, PL::NUP>([&](auto uc) { st.template advance<decltype(uc)::value>(); });
         // the next iteration's points, requested behind the ring's last LDS-DMA requests and ahead of everything that is left to do here
         int tg_n = tg;
         long long grp_n = grp, b0_n = b0;
@@ -499,6 +523,38 @@ __global__ void __launch_bounds__(WAVES * 64, 1) net_kernel_x16(const NetArgs a)
 #endif
 }
 
+// the LDS request of a launch (x16_lds_bytes, nrnerf_plan.h), with or without the resident block
+template <class P, class A, bool VIEWS>
+static size_t x16_launch_lds(int S, bool fused, bool sample, bool resident) {
+    size_t res_bytes = 0;
+    if constexpr (X16Res<A, VIEWS, false>::OK) res_bytes = resident ? (size_t)ResX16<P, A>::BYTES : 0;
+    return x16_lds_bytes(P::UNIT_BYTES, PlanX16<P, A, VIEWS>::NTILES, X16Cfg<A>::WAVES, X16Cfg<A>::NB, S, fused, sample, res_bytes);
+}
+// which variant a launch takes: the resident-slice one when the instantiation has it, the call does not opt out and the request fits the CU's LDS
+template <class P, class A, bool VIEWS, bool SAMPLE>
+static bool x16_resident_fits(const NetArgs& a) {
+    if (!X16Res<A, VIEWS, SAMPLE>::OK || a.no_resident) return false;
+    return x16_launch_lds<P, A, VIEWS>(a.S, a.fuse_on != 0, SAMPLE, true) <= X16_LDS_MAX;
+}
+template <class P, class A, int EPL, bool VIEWS, bool SAMPLE, bool RES>
+static hipError_t x16_launch_kernel(const NetArgs& a, size_t lds, int grid, hipStream_t stream) {
+    constexpr int WAVES = X16Cfg<A>::WAVES, NB = X16Cfg<A>::NB;
+    auto kern = net_kernel_x16<P, A, WAVES, EPL, VIEWS, SAMPLE, RES>;
+    static bool attr_set[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        // the largest request any launch can make: ring (+ resident block) + bias table + the fused stages at bpr = 15 (RW = NB)
+        const size_t lds_max = x16_launch_lds<P, A, VIEWS>(0, false, false, RES) + (size_t)WAVES * NB * 15 * 256 + 256 +
+                               (SAMPLE ? (size_t)WAVES * (2 * 64 * EPL + 260) * sizeof(float) : 0);
+        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_max < X16_LDS_MAX ? lds_max : X16_LDS_MAX));
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a);
+    return hipGetLastError();
+}
+
 template <class P, class A, int EPL, bool VIEWS = false, bool SAMPLE = false>
 static hipError_t launch_net_x16_t(const NetArgs& a, int num_cus, hipStream_t stream) {
     constexpr int WAVES = X16Cfg<A>::WAVES;
@@ -508,35 +564,22 @@ static hipError_t launch_net_x16_t(const NetArgs& a, int num_cus, hipStream_t st
     if ((a.fuse_on != 0) != (EPL > 0) || (EPL > 0 && (a.S + 63) / 64 != EPL)) return hipErrorInvalidValue;      // (the dispatcher's job)
     const int bpr = (a.S + 15) / 16;
     const int RW = (bpr % NB == 0) ? 1 : ((2 * bpr) % NB == 0 ? 2 : NB);
-    size_t lds = (size_t)RING * P::UNIT_BYTES + (size_t)PL::NTILES * 16 * sizeof(float) + 128;     // ring | bias table | a tile of zeros | mailbox
     if (a.fuse_on) {
         if (a.S > 256 || (a.fuse.n_importance != 0) != SAMPLE || a.fuse.S != a.S) return hipErrorInvalidValue;
-        lds += (size_t)WAVES * RW * bpr * 16 * 16 + 256;            // the waves' raw stages + the compositing arguments
-        if (SAMPLE) {
-            if (a.S + a.fuse.n_importance > 256 || !a.fuse.z_out) return hipErrorInvalidValue;
-            lds += (size_t)WAVES * (2 * 64 * EPL + 260) * sizeof(float);
-        }
+        if (SAMPLE && (a.S + a.fuse.n_importance > 256 || !a.fuse.z_out)) return hipErrorInvalidValue;
     }
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    auto kern = net_kernel_x16<P, A, WAVES, EPL, VIEWS, SAMPLE>;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        // the largest request any launch can make: ring + bias table + the fused stages at bpr = 15 (RW = NB)
-        const size_t lds_max = (size_t)RING * P::UNIT_BYTES + (size_t)PL::NTILES * 16 * sizeof(float) + 128 + (size_t)WAVES * NB * 15 * 256 + 256 +
-                               (SAMPLE ? (size_t)WAVES * (2 * 64 * EPL + 260) * sizeof(float) : 0);
-        hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_max < 160 * 1024 ? lds_max : 160 * 1024));
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
+    const size_t lds = x16_launch_lds<P, A, VIEWS>(a.S, a.fuse_on != 0, SAMPLE, false);
+    if (lds > X16_LDS_MAX) return hipErrorInvalidValue;
     long long want;
     if (a.fuse_on) want = ((long long)a.n_rays + WAVES * RW - 1) / (WAVES * RW);          // groups of WAVES * RW whole rays
     else want = ((long long)a.n_rays * bpr + WAVES * NB - 1) / (WAVES * NB);
     if (want <= 0) return hipSuccess;
     const int grid = (int)(want < num_cus ? want : num_cus);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), lds, stream, a);
-    return hipGetLastError();
+    // the resident-slice variant wherever it exists and its request fits (not: 256 fused samples, stages of RW = NB rays); NetArgs::no_resident opts out
+    if constexpr (X16Res<A, VIEWS, SAMPLE>::OK) {
+        if (x16_resident_fits<P, A, VIEWS, SAMPLE>(a)) return x16_launch_kernel<P, A, EPL, VIEWS, SAMPLE, true>(a, x16_launch_lds<P, A, VIEWS>(a.S, a.fuse_on != 0, SAMPLE, true), grid, stream);
+    }
+    return x16_launch_kernel<P, A, EPL, VIEWS, SAMPLE, false>(a, lds, grid, stream);
 }
 
 }  // namespace nrn

@@ -49,6 +49,20 @@ long long x16_rays_per_group(int arch, int S) {
     const int RW = (bpr % NB == 0) ? 1 : ((2 * bpr) % NB == 0 ? 2 : NB);
     return (long long)WAVES * RW;
 }
+bool x16_takes_resident(int precision, int arch, bool views, const NetArgs& a) {
+    if (views || arch != 0 || (a.fuse_on && a.fuse.n_importance > 0)) return false;
+    if (precision == PREC_BF16) return x16_resident_fits<PolBF16, ArchDefault, false, false>(a);
+    if (precision == PREC_F16) return x16_resident_fits<PolF16, ArchDefault, false, false>(a);
+    return false;
+}
+size_t x16_lds_request(int precision, int arch, bool views, int S, bool fused, bool sample, bool resident) {
+    if ((precision != PREC_BF16 && precision != PREC_F16) || (arch != 0 && arch != 5) || (views && arch != 0) || S < 1) return 0;
+    if (resident && (views || sample || arch != 0)) return 0;          // (no such kernel)
+    if (arch == 5) return x16_launch_lds<PolBF16, ArchNarrow, false>(S, fused, sample, false);
+    if (views) return x16_launch_lds<PolBF16, ArchDefault, true>(S, fused, sample, false);
+    if (precision == PREC_BF16) return x16_launch_lds<PolBF16, ArchDefault, false>(S, fused, sample, resident);
+    return x16_launch_lds<PolF16, ArchDefault, false>(S, fused, sample, resident);
+}
 hipError_t launch_net_x16_e1(int, int, bool, const NetArgs&, int, hipStream_t);
 hipError_t launch_net_x16_e2(int, int, bool, const NetArgs&, int, hipStream_t);
 hipError_t launch_net_x16_e3(int, int, bool, const NetArgs&, int, hipStream_t);

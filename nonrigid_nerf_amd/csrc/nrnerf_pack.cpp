@@ -1308,6 +1308,23 @@ int pack_host_image(const nrnerf_model_desc* desc, int which, PackedPass& pk) {
         if (!x16_eligible(*desc, *mm, /*any_16bit=*/true)) return NRNERF_ERR_UNSUPPORTED;
         rc = NRNERF_OK;
         pack_x16(*desc, *mm, pk);
+    } else if (which == 15) {                    // the resident-slice table of image 10 (ResX16, nrnerf_plan.h): no image, the table as the unit table
+        const nrnerf_mlp_desc* mm = desc->fine ? desc->fine : desc->coarse;
+        if (!x16_eligible(*desc, *mm, /*any_16bit=*/true) || mm->use_viewdirs || mm->width != 256) return NRNERF_ERR_UNSUPPORTED;
+        rc = NRNERF_OK;
+        auto table = [&](auto rs) {
+            using RS = decltype(rs);
+            pk = PackedPass{};
+            pk.frag_bytes = Shape16::FRAG_BYTES; pk.slot_bytes = Shape16::UNIT_BYTES;
+            pk.unit_off.assign(1, (uint32_t)RS::NRES);
+            for (int r = 0; r < RS::NRES; ++r) pk.unit_off.push_back((uint32_t)RS::T.res_src[r]);
+            pk.unit_off.push_back((uint32_t)RS::NUNITS);
+            pk.unit_off.push_back((uint32_t)Shape16::UNIT_FRAGS);
+            for (int u = 0; u < RS::NUNITS; ++u) pk.unit_off.push_back((uint32_t)(RS::unit_src_bytes(u) / 16));
+            pk.nunits = (int)pk.unit_off.size() - 1;
+        };
+        if (desc->precision == NRNERF_PREC_F16) table(ResX16<Shape16, ArchDefault>{});      // (the two 16-bit modes share the plan: one table)
+        else table(ResX16<Shape16Fast, ArchDefault>{});
     } else if (which == 13 || which == 14) {    // backward-data programs of the run-time-parameterised kernel (training): 13 = coarse, 14 = fine
         GenProgram gb, gc, gf;
         rc = gen_pack_all(*desc, nullptr, gb, gc, gf);

@@ -11,6 +11,7 @@
 // fixed permutation of the k index -- is exactly the B-operand layout of the next layer.  The
 // permutation is folded into the packed weights here, so activations never leave registers.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #if defined(__HIPCC__)
@@ -534,6 +535,75 @@ struct PlanX16 {
     static constexpr int L_HEAD = NLAYERS - 1;                 // output_linear, or (VIEWS) rgb_linear
     static constexpr int L_VIEWS = NLAYERS - 2;                // (VIEWS) [views_linears[0] o feature_linear; alpha_linear]
 };
+// The RESIDENT SLICE of the plain-headed trunk's image (net_kernel_x16<.., RES>, nrnerf_net_x16.h): the fragments whose B operand is not a
+// W-wide hidden activation -- the first layer (NS_E k-steps), the skip layer's NS_E encoding k-steps and the head's one tile -- are few and the
+// same for every sample, so a workgroup copies them to LDS once and the ring carries only the W x W blocks.  The image is NOT repacked: the
+// table below says, per image fragment, where the kernel reads it (slot of the resident block, in image order | ring fragment index, in
+// image order), and per ring unit where in the image its UNIT_FRAGS consecutive fragments start.  At W = 256: 72 resident fragments,
+// 896 = 7 x 128 ring fragments = 56 units -- a multiple of RING, so the stream needs no padding units and every hidden layer is 8 whole units.
+// The skip layer's stream order per tile pair is (t0,s0) (t1,s0) (t0,s1) (t1,s1) + 16 hidden-k-step fragments: its units are the eight
+// 16-fragment runs at stride 20 fragments, offset 4.
+struct ResTable {
+    static constexpr int MAXF = 1024, MAXU = 64, MAXR = 96;
+    short res_of[MAXF];         // image fragment -> slot of the resident block, -1: streamed
+    short ring_of[MAXF];        // image fragment -> ring fragment index, -1: resident
+    short res_src[MAXR];        // resident slot -> image fragment
+    short unit_src[MAXU];       // ring unit -> its first image fragment
+    int nres, nring, nunits;
+    bool whole_units;           // every ring unit is UNIT_FRAGS consecutive image fragments, and there is no partial last unit
+};
+template <class SH, class A>
+constexpr ResTable build_res_table() {
+    using PL = PlanX16<SH, A, false>;
+    static_assert(PL::NFRAGS <= ResTable::MAXF, "table sizes");
+    ResTable R{};
+    bool whole = true;
+    int g = 0;
+    for (int l = 0; l < PL::TB.nlayers; ++l) {
+        const LayerSpec spec = PL::TB.layers[l];
+        const int npair = spec.nt / 2, Q = spec.nt * spec.ns;
+        for (int q = 0; q < Q; ++q, ++g) {
+            const int slab = q < npair * 2 * spec.ns ? (q % (2 * spec.ns)) / 2 : q - npair * 2 * spec.ns;      // (SeqPos::slab, nrnerf_net_impl.h)
+            const bool res = spec.kind == LK_TR_IN || spec.kind == LK_HEAD || (spec.kind == LK_TR_SKIP && slab < PL::NS_E);
+            R.res_of[g] = -1; R.ring_of[g] = -1;
+            if (res) {
+                if (R.nres < ResTable::MAXR) R.res_src[R.nres] = (short)g;
+                R.res_of[g] = (short)R.nres++;
+            } else {
+                const int u = R.nring / SH::UNIT_FRAGS, k = R.nring % SH::UNIT_FRAGS;
+                if (k == 0 && u < ResTable::MAXU) R.unit_src[u] = (short)g;
+                if (u >= ResTable::MAXU || g != R.unit_src[u] + k) whole = false;
+                R.ring_of[g] = (short)R.nring++;
+            }
+        }
+    }
+    R.nunits = R.nring / SH::UNIT_FRAGS;
+    R.whole_units = whole && R.nring % SH::UNIT_FRAGS == 0 && R.nres <= ResTable::MAXR && g == PL::NFRAGS;
+    return R;
+}
+template <class SH, class A>
+struct ResX16 {
+    static constexpr ResTable T = build_res_table<SH, A>();
+    static constexpr int NRES = T.nres, NRING = T.nring, NUNITS = T.nunits;
+    static constexpr int BYTES = NRES * SH::FRAG_BYTES;                // the resident block in LDS
+    static_assert(T.whole_units, "every ring unit is one contiguous UNIT_BYTES run of the image");
+    static_assert(NRES + NRING == PlanX16<SH, A, false>::NFRAGS, "resident and ring fragments partition the image");
+    static_assert(NUNITS % RING == 0 && NUNITS >= RING, "the ring carries whole periods: unit 0 lands in slot 0 without padding units");
+    static constexpr bool resident(int g) { return T.res_of[g] >= 0; }
+    static constexpr int unit_src_bytes(int v) { return T.unit_src[v] * SH::FRAG_BYTES; }
+};
+// the LDS request of a net_kernel_x16 launch of S samples per ray, WAVES waves of NB blocks: ring | (resident) the resident block | bias table
+// [tiles][16] | a tile of zeros + the mailbox | (fused) the waves' raw stages + the compositing arguments | (sample) the coarse epilogue's scratch
+constexpr NRN_HD size_t x16_lds_bytes(int unit_bytes, int ntiles, int waves, int nb, int S, bool fused, bool sample, size_t resident_bytes) {
+    const int bpr = (S + 15) / 16, epl = (S + 63) / 64;
+    const int rw = (bpr % nb == 0) ? 1 : ((2 * bpr) % nb == 0 ? 2 : nb);
+    size_t lds = (size_t)RING * unit_bytes + resident_bytes + (size_t)ntiles * 16 * sizeof(float) + 128;
+    if (fused) lds += (size_t)waves * rw * bpr * 16 * 16 + 256;
+    if (fused && sample) lds += (size_t)waves * (2 * 64 * epl + 260) * sizeof(float);
+    return lds;
+}
+constexpr size_t X16_LDS_MAX = 160 * 1024;
+
 // reference element of fragment (layer kind, tile t, lane row r, k-step s, group g, element e): (row, column), -1 = zero
 // (LK_VIEWS: rows / columns of the FOLDED layer -- hidden columns first, then the direction encoding's; its last tile, the alpha
 //  row, is the packer's business: another nn.Linear)

@@ -413,6 +413,13 @@ class Model:
     def profile_begin(self):
         _lib.check(self.lib.nrnerf_profile_begin(self.handle), "nrnerf_profile_begin")
 
+    def resident_launches(self) -> dict:
+        """Launches of the 16x16x32 trunk kernel's resident-slice variant per profile slot since ``profile_begin`` (the profile's kernel
+        names do not say which variant ran): ``{"net_coarse": n, "net_fine": n, ...}``."""
+        n = (C.c_int32 * len(_lib.KERNEL_NAMES))()
+        _lib.check(self.lib.nrnerf_resident_launches(self.handle, n), "nrnerf_resident_launches")
+        return {name: int(n[i]) for i, name in enumerate(_lib.KERNEL_NAMES)}
+
     def profile_end(self) -> dict:
         p = _lib.Profile()
         _lib.check(self.lib.nrnerf_profile_end(self.handle, C.byref(p)), "nrnerf_profile_end")
