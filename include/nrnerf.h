@@ -489,7 +489,9 @@ int nrnerf_bender_backward(const nrnerf_model* model, const nrnerf_bender_args* 
  * origin + direction * z, latent code) are formed from rays / latents / z as in nrnerf_bender_args.  Contraction: exact
  * fp32 for a model created with NRNERF_PREC_F32 (fp32 saved arrays); otherwise the saved arrays are bf16 and are contracted
  * on the bf16 matrix pipe with fp32 accumulation, the fp32 rows (dz_out4, points, latent codes) rounded to bf16 in registers
- * (the gradients entering come out of a bf16 trunk there).  The 16-bit route addresses every array by 32-bit byte offsets:
+ * (the gradients entering come out of a bf16 trunk there); that rounding is the products' alone: db is the fp32 sum of dz as
+ * stored, dz_out4 unrounded.  A wave whose range of samples is empty still writes its slot, all zeros: n_partials may exceed
+ * what n_rays * n_samples can fill.  The 16-bit route addresses every array by 32-bit byte offsets:
  * n_rays * n_samples * 256 bytes must stay below 4 GiB (NRNERF_ERR_INVALID beyond, also from nrnerf_bender_divergence_backward,
  * which forms its weight gradients the same way). */
 #define NRNERF_BENDER_WGRAD_SLOT (64 * 64 + 64)

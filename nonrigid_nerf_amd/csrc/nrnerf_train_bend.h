@@ -21,6 +21,19 @@
 
 namespace nrn {
 
+// One product or one sum, rounded once, that stays that: __fmul_rn / __fadd_rn are plain operators in this toolchain's headers, and
+// with contraction allowed (the default for device code) o + d z written with them compiled to ONE fused multiply-add.  The training
+// entry points promise the reference's two roundings (run_nerf_helpers.py:567-570, train.py:871-873: separate torch ops), and the
+// point must be the same number in the forward kernel and in the weight-gradient kernels that form it again.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
 template <class PE, int T, class ACT>
 __device__ __forceinline__ void pack_lin(const f32x16& acc, ACT& out) {      // D tile -> next B operand, no activation
     static_for<0, PE::SP>([&](auto uc) {
@@ -63,7 +76,7 @@ __global__ void __launch_bounds__(256, 2) bend_fwd_train(const BendTrainArgs a) 
         const size_t so = (size_t)ray * S + (ok ? sidx : S - 1);
         const float* rp = a.rays + (size_t)ray * a.ray_stride;
         const float z = a.z[so];
-        float p[3] = {__fadd_rn(rp[0], __fmul_rn(rp[3], z)), __fadd_rn(rp[1], __fmul_rn(rp[4], z)), __fadd_rn(rp[2], __fmul_rn(rp[5], z))};
+        float p[3] = {add_rn(rp[0], mul_rn(rp[3], z)), add_rn(rp[1], mul_rn(rp[4], z)), add_rn(rp[2], mul_rn(rp[5], z))};
         const float* lat = a.latents + (size_t)ray * a.lat_stride;
         auto binval = [&](auto idxc) -> float {
             constexpr int idx = decltype(idxc)::value;
@@ -127,9 +140,9 @@ __global__ void __launch_bounds__(256, 2) bend_fwd_train(const BendTrainArgs a) 
         float bent[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            float mo = __fmul_rn(mask, off[c]);                                            // rnh:567
-            if (a.knobs.has_scaling) mo = __fmul_rn(mo, a.knobs.scaling);                  // rnh:568-569
-            bent[c] = __fadd_rn(p[c], mo);                                                 // rnh:570
+            float mo = mul_rn(mask, off[c]);                                            // rnh:567
+            if (a.knobs.has_scaling) mo = mul_rn(mo, a.knobs.scaling);                  // rnh:568-569
+            bent[c] = add_rn(p[c], mo);                                                 // rnh:570
         }
         if (ok && h == 0) {
             *(f32x4*)(a.bent4 + so * 4) = f32x4{bent[0], bent[1], bent[2], mask};
@@ -310,6 +323,7 @@ __global__ void __launch_bounds__(256, 2) bend_div_fwd(const BendDivArgs a) {
         float p[3], ev[3];
         const float* lat;
         if (a.rays) {                   // ray mode (BendDivArgs): the sample's point and the ray's unit direction, computed here
+                                        // (nrnerf_render's mode: its arithmetic stays as the network kernels', which it must match)
             const size_t ray = so / (size_t)a.S;
             const int k = (int)(so - ray * (size_t)a.S);
             const float* rp = a.rays + ray * (size_t)a.ray_stride;
@@ -441,9 +455,9 @@ __global__ void __launch_bounds__(256, 2) bend_div_fwd(const BendDivArgs a) {
                 float bent[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    float mo = __fmul_rn(mask, off[c]);
-                    if (a.knobs.has_scaling) mo = __fmul_rn(mo, a.knobs.scaling);
-                    bent[c] = __fadd_rn(p[c], mo);
+                    float mo = mul_rn(mask, off[c]);
+                    if (a.knobs.has_scaling) mo = mul_rn(mo, a.knobs.scaling);
+                    bent[c] = add_rn(p[c], mo);
                 }
                 *(f32x4*)(a.bent4 + so * 4) = f32x4{bent[0], bent[1], bent[2], mask};
             }
@@ -660,7 +674,7 @@ __global__ void __launch_bounds__(256) bend_wgrad(const BendWgradArgs a) {
                     const float* rp = a.rays + (size_t)ray * a.ray_stride;
                     const float* lp = a.latents + (size_t)ray * a.lat_stride;
                     float v0 = 0.0f, v1 = 0.0f;
-                    if (ok && gb0) v0 = (i < 3) ? __fadd_rn(rp[i], __fmul_rn(rp[3 + i], a.z[s])) : lp[i - 3];
+                    if (ok && gb0) v0 = (i < 3) ? add_rn(rp[i], mul_rn(rp[3 + i], a.z[s])) : lp[i - 3];
                     if (ok && gb1) v1 = lp[29 + i];
                     bv[u][0] = v0;
                     bv[u][1] = v1;
@@ -790,7 +804,7 @@ __global__ void __launch_bounds__(256, 2) bend_wgrad16(const BendWgradArgs a) {
                         for (int e = 0; e < 8; ++e) ra[e][1] = __builtin_amdgcn_raw_buffer_load_b32(rd, bd + od1 + e * rbd, 0, 0);
                     }
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) rb[e][0] = __builtin_bit_cast(unsigned, (i < 3) ? __fadd_rn(ro[e], __fmul_rn(rdv[e], rz[e])) : l0[e]);
+                    for (int e = 0; e < 8; ++e) rb[e][0] = __builtin_bit_cast(unsigned, (i < 3) ? add_rn(ro[e], mul_rn(rdv[e], rz[e])) : l0[e]);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) ra[e][0] = __builtin_amdgcn_raw_buffer_load_b32(rd, bd + od0 + e * rbd, 0, 0);
