@@ -1284,6 +1284,67 @@ typedef struct nrnerf_sh_volume_render_args {
 } nrnerf_sh_volume_render_args;
 int nrnerf_sh_volume_render(const nrnerf_sh_volume_render_args* args, void* hip_stream);
 
+/* ---- ABI 10 (additions): the adjoint of the colour sum -- what refines the coefficients of a view-dependent bake on images.
+ *
+ * THE FUNCTION THAT IS DIFFERENTIATED is the direction-dependent part of a sample's colour logit above,
+ *     s_c(b, d) = sum over k = 1 .. K - 1 of Y_k(d) * v_{k,c}(b),     c = 0 .. 2,  K = (L + 1)^2,  L = 1 or 2,
+ * v the sh array at the bent point b by THE VALUE AT A POINT (the same cell i_c, the same fractions f_c, half widened first) and Y_k THE BASIS
+ * above as polynomials in an unconstrained d: no projection onto the sphere.  The `raw` part of the logit, and sigma, have their adjoint in
+ * nrnerf_grid_lookup_backward; this call does not repeat it.  nrnerf_sh_lookup_backward takes the bent points points4 [N, S, 4] and the
+ * cotangents g_raw [N, S, 4] of the samples' logits (channels 0 .. 2 are read: g_c) and returns the gradients of sum over the samples of
+ * <g, s> (csrc/nrnerf_sh_grad.h), all in fp32, every product rounded once, every sum an fma:
+ *     d_sh[corner j, 3 (k - 1) + c] += w_j * (Y_k(d) * g_c)      w_j = ((wx * wy) * wz) as in the adjoint of the lookup; float32 whatever the
+ *         storage of sh; ADDED INTO; for L = 1 the channels 9 .. 11 are never touched;
+ *     d_points, position part:  s_axis * d/df_axis of the trilinear interpolation of the eight scalars u_j = sum over the channels, ascending, of
+ *         (Y_k * g_c) * corner_j[3 (k - 1) + c], by the adjoint of the lookup's dv/df_x, dv/df_y, dv/df_z forms, ONE-SIDED ON A FACE as there;
+ *     d_dirs[axis] = sum over k, ascending, of t_k * dY_k/d axis,   t_k = sum over c of g_c * v_{k,c}(b)  (v as the forward interpolates it),
+ *         dY1 = (0, -C1, 0)   dY2 = (0, 0, C1)   dY3 = (-C1, 0, 0)           C1 = 0.4886025119029199, C2 = 1.0925484305920792,
+ *         dY4 = C2 (y, x, 0)  dY5 = -C2 (0, z, y)  dY7 = -C2 (z, 0, x)        C20 = 0.31539156525252005, C22 = 0.5462742152960396
+ *         dY6 = C20 (-2x, -2y, 4z)   dY8 = C22 (2x, -2y, 0);
+ *     an EMPTY sample (outside the box, or NaN) adds nothing to d_sh; its d_dirs is 0 and the position part of its d_points is 0.
+ * THE DIRECTION is computed in the call exactly as nrnerf_sh_volume_render computes it, by the same `direction_mode`:
+ *     NRNERF_SH_DIRECTION_RAY: d = ray_d / |ray_d| (columns 3 .. 5 of `rays`).  Nothing flows into d_points from the direction: rays carry
+ *         no gradient.  d_dirs is the gradient with respect to d itself.
+ *     NRNERF_SH_DIRECTION_DIFFERENCES: for i >= 1  e_i = b_i - b_{i-1}, n_i = |e_i|, d_i = e_i / (n_i + 1e-6), d_0 = d_1, over all samples, empty
+ *         or not, and the chain back to the points is part of the call:  G_i = d_dirs[i] for i >= 2, G_1 = d_dirs[1] + d_dirs[0],
+ *             E_i = G_i / (n_i + 1e-6) - e_i * ((G_i . e_i) / ((n_i * (n_i + 1e-6)) * (n_i + 1e-6))),
+ *             d_points[i] += E_i for i >= 1,   d_points[i] -= E_{i+1} for i <= S - 2.
+ *         WHERE n_i == 0 (coincident bent points) THE SECOND TERM OF E_i IS TAKEN AS 0: every output stays finite.  An empty sample still
+ *         receives the direction part through its neighbours' directions.  d_points needs the d_dirs buffer, the workspace of the chain.
+ * d_sh is ADDED INTO (the caller zeroes it, or keeps accumulating) with float32 atomic adds to global memory.  THE ORDER OF ITS SUMS IS NOT
+ * FIXED: like d_grid of nrnerf_grid_lookup_backward it is not "the same bits on every run" -- two runs differ by the rounding of a reordered
+ * float32 sum.  d_points and d_dirs have one writer per element and a fixed operation order: the same bits on every run, alone or together.
+ * With d_points and d_dirs NULL the coefficients are not read (`sh` may be NULL).  Up to three kernels on the stream, in this order: the
+ * scatter (d_sh), one thread per sample for the position part and d_dirs, one thread per sample for the chain (DIFFERENCES with d_points);
+ * no LDS, no workspace beyond d_dirs.  Device pointers only, asynchronous on the stream, allocates nothing; runs on the device that owns
+ * d_sh (d_points, else d_dirs, when d_sh is NULL).  Gradients of rays or depths, degree 3 and second derivatives are out of scope.
+ * Checks, in this order: NRNERF_ERR_INVALID for a NULL record or a wrong struct_size; n_rays < 0, n_samples outside 1 ..
+ * NRNERF_MAX_SAMPLES; sh_degree other than 1 or 2; an unknown direction_mode; DIFFERENCES with n_samples == 1; RAY with ray_stride < 6; a
+ * g < 2, a max_c that is not > min_c (NaN included), an unknown sh_dtype.  NRNERF_ERR_UNSUPPORTED for more than 2^30 vertices or 2^31 or
+ * more samples.  Then n_rays == 0 answers NRNERF_OK without a launch.  Then NRNERF_ERR_INVALID for a NULL points4 / g_raw, RAY with NULL
+ * rays; nothing to write (d_sh, d_points and d_dirs all NULL); d_points or d_dirs without sh; DIFFERENCES with d_points but no d_dirs;
+ * and -- the first HIP calls -- memory that is not device memory of one device, a points4 / g_raw that is not 16-byte aligned, an sh (when
+ * it is read) that is not aligned to four channels. */
+typedef struct nrnerf_sh_lookup_backward_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_sh_lookup_backward_args) */
+    int32_t n_rays, n_samples;  /* N >= 0, 1 <= S <= NRNERF_MAX_SAMPLES (DIFFERENCES: 2 <= S) */
+    const float* rays;          /* [N, ray_stride], the direction in columns 3 .. 5; read in RAY mode only */
+    int32_t ray_stride;         /* RAY: >= 6 */
+    const float* points4;       /* [N, S, 4] the bent points (xyz first), 16-byte aligned */
+    int32_t direction_mode;     /* NRNERF_SH_DIRECTION_DIFFERENCES / NRNERF_SH_DIRECTION_RAY */
+    const void* sh;             /* [gz, gy, gx, 12 * sh_degree] coefficients, float32 or half; read for d_points / d_dirs only */
+    int32_t sh_dtype;           /* NRNERF_VOLUME_F32 / NRNERF_VOLUME_F16 */
+    int32_t sh_degree;          /* 1 or 2 */
+    int32_t g[3];               /* gx, gy, gz, each >= 2 */
+    float min_point[3];         /* the box, as in nrnerf_grid_points; max_c > min_c */
+    float max_point[3];
+    const float* g_raw;         /* [N, S, 4] cotangents of the samples' logits (raw of nrnerf_sh_volume_render), 16-byte aligned; channels 0 .. 2 */
+    float* d_sh;                /* in/out float32 [gz, gy, gx, 12 * sh_degree], added into, or NULL */
+    float* d_points;            /* out [N, S, 3], or NULL */
+    float* d_dirs;              /* out [N, S, 3], or NULL */
+} nrnerf_sh_lookup_backward_args;
+int nrnerf_sh_lookup_backward(const nrnerf_sh_lookup_backward_args* args, void* hip_stream);
+
 /* ---- ABI 10 (additions): occupancy masks -- a baked render that asks for nothing where the volume is empty.
  *
  * Every sample inside the box costs the eight corners of `raw` and of every chunk of `sh`, and most of a scene's box is empty.  Whether a

@@ -437,6 +437,16 @@ class GridLookupBackwardArgs(C.Structure):
                 ("g_value", C.c_void_p), ("d_grid", C.c_void_p), ("d_points", C.c_void_p)]
 
 
+class ShLookupBackwardArgs(C.Structure):
+    """nrnerf_sh_lookup_backward_args (ABI 10 additions): the adjoint of the spherical-harmonic colour sum -- d sh (added into, float32), d points
+    and d directions from the cotangents of the samples' colour logits."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_rays", C.c_int32), ("n_samples", C.c_int32),
+                ("rays", C.c_void_p), ("ray_stride", C.c_int32), ("points4", C.c_void_p), ("direction_mode", C.c_int32),
+                ("sh", C.c_void_p), ("sh_dtype", C.c_int32), ("sh_degree", C.c_int32), ("g", C.c_int32 * 3),
+                ("min_point", C.c_float * 3), ("max_point", C.c_float * 3),
+                ("g_raw", C.c_void_p), ("d_sh", C.c_void_p), ("d_points", C.c_void_p), ("d_dirs", C.c_void_p)]
+
+
 class BendPointsArgs(C.Structure):
     """nrnerf_bend_points_args (ABI 10 additions): the bender step of nrnerf_query by itself, points -> bent4 (bent xyz, rigidity)."""
     _fields_ = [("struct_size", C.c_uint32), ("n_rows", C.c_int32), ("n_samples", C.c_int32),
@@ -501,6 +511,7 @@ EXPORTS = {
     "nrnerf_warped_volume_render": (C.c_int, [C.POINTER(WarpedVolumeRenderArgs), C.c_void_p]),
     "nrnerf_grid_lookup_backward": (C.c_int, [C.POINTER(GridLookupBackwardArgs), C.c_void_p]),
     "nrnerf_sh_volume_render": (C.c_int, [C.POINTER(ShVolumeRenderArgs), C.c_void_p]),
+    "nrnerf_sh_lookup_backward": (C.c_int, [C.POINTER(ShLookupBackwardArgs), C.c_void_p]),
     "nrnerf_occupancy_words": (C.c_int64, [C.POINTER(C.c_int32), C.c_int32]),
     "nrnerf_occupancy_build": (C.c_int, [C.POINTER(OccupancyBuildArgs), C.c_void_p]),
     "nrnerf_culled_volume_render": (C.c_int, [C.POINTER(CulledVolumeRenderArgs), C.c_void_p]),

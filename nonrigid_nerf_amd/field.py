@@ -1359,9 +1359,9 @@ def grid_lookup(grid, min_point, max_point, points):
     differentiable with respect to ``grid`` and ``points`` (``nrnerf_grid_lookup_backward``).  A point outside the box, or NaN, has value 0 and
     no gradient; on a cell face the gradient is the one of the cell the lookup picks (the upper cell, the last one on the top face).  The
     gradient of ``grid`` is summed in float32 with atomic adds -- its last bits can differ between runs -- and cast to the grid's dtype once.
-    A volume record with ``"sh"`` in place of ``grid`` raises ``Unsupported``: gradients of spherical-harmonic coefficients are out of scope."""
+    A volume record with ``"sh"`` in place of ``grid`` raises ``Unsupported``: ``sh_lookup`` is the lookup of such a record under autograd."""
     if _has_sh(grid):
-        raise R.Unsupported("a volume record with spherical-harmonic coefficients: gradients of the coefficients are out of scope")
+        raise R.Unsupported("a volume record with spherical-harmonic coefficients: its gradients are sh_lookup's, not grid_lookup's")
     if not torch.is_tensor(grid) or grid.device.type != "cuda":
         raise R.Unsupported("the grid is not on a ROCm device")
     _, lo, hi, _ = _grid_parts({"grid": grid, "min_point": min_point, "max_point": max_point}, "grid", "grid")
@@ -1386,7 +1386,7 @@ def render_baked_train(volume, warp, rays, *, N_samples, z_vals=None, lindisp=Fa
     gradient."""
     from .training import _Composite
     if _has_sh(volume):
-        raise R.Unsupported("a view-dependent bake has no gradient: gradients of spherical-harmonic coefficients are out of scope")
+        raise R.Unsupported("a view-dependent bake has no gradient here: render_sh_train differentiates its coefficients")
     if not torch.is_tensor(rays) or rays.device.type != "cuda":
         raise R.Unsupported("rays are not on a ROCm device")
     _, lo, hi, _ = _grid_parts(volume, "raw", "volume")
@@ -1443,28 +1443,38 @@ def refine_bake(volume, warps, frames, *, steps, lr, batch_rays=None, params=("v
     one grid, which every index then means), or ``None`` for straight rays.  ``params``: ``"volume"`` and / or ``"warp"``, what is refined; the
     refined grids are kept in float32 during the loop and come back in their records' dtype.  ``render``: ``render_baked_train``'s keywords
     (``N_samples``, ``lindisp``, ``white_bkgd``, the knobs).  Returns ``(volume record, warps record or None, [loss per step])``; the inputs are
-    not modified.  No scheduler, no checkpointing.  A volume record with ``"sh"`` (a view-dependent bake) raises ``Unsupported``: gradients of
-    the coefficients are out of scope."""
+    not modified.  No scheduler, no checkpointing.  A volume record with ``"sh"`` (a view-dependent bake) raises ``Unsupported``:
+    ``refine_sh_bake`` refines such a record."""
     if _has_sh(volume):
-        raise R.Unsupported("a view-dependent bake cannot be refined: gradients of spherical-harmonic coefficients are out of scope")
-    params = tuple(params)
-    if not params or any(k not in ("volume", "warp") for k in params):
-        raise ValueError(f"params names 'volume' and / or 'warp', got {params}")
+        raise R.Unsupported("a view-dependent bake cannot be refined by refine_bake (gradients of its coefficients: refine_sh_bake)")
+    return _refine_loop(volume, warps, frames, steps, lr, batch_rays, tuple(params), ("volume", "warp"), optimizer, seed, render_baked_train,
+                        render, "refine_bake")
+
+
+def _refine_loop(volume, warps, frames, steps, lr, batch_rays, params, allowed, optimizer, seed, render_fn, render, who):
+    """The loop ``refine_bake`` and ``refine_sh_bake`` share: float32 copies of the grids named by ``params`` as leaves, per step one frame (and
+    of it one batch of rays), the mean squared error of ``render_fn``'s ``rgb_map``, one optimiser step.  ``(volume record, warps record or
+    None, [loss per step])``."""
+    if not params or any(k not in allowed for k in params):
+        raise ValueError(f"params names {' and / or '.join(repr(k) for k in allowed)}, got {params}")
     if "warp" in params and warps is None:
         raise ValueError("there is no warp to refine")
     if optimizer not in ("adam", "sgd"):
         raise ValueError(f"optimizer is 'adam' or 'sgd', got {optimizer!r}")
     if len(frames) < 1:
-        raise ValueError("refine_bake needs at least one frame")
+        raise ValueError(f"{who} needs at least one frame")
     dev = volume["raw"].device
     vol = volume["raw"].detach().to(torch.float32).clone().requires_grad_("volume" in params)
+    sh = None
+    if "sh" in allowed:
+        sh = volume["sh"].detach().to(torch.float32).clone().requires_grad_("sh" in params)
     grids = None
     if warps is not None:
         grids = warps["warp"]
         if not torch.is_tensor(grids) or grids.dim() not in (4, 5):
             raise ValueError("warps must hold one grid [Gz, Gy, Gx, 4] or a stack [F, Gz, Gy, Gx, 4]")
         grids = grids.detach().to(torch.float32).clone().requires_grad_("warp" in params)
-    leaves = [t for t in (vol, grids) if t is not None and t.requires_grad]
+    leaves = [t for t in (vol, sh, grids) if t is not None and t.requires_grad]
     opt = torch.optim.Adam(leaves, lr=lr) if optimizer == "adam" else torch.optim.SGD(leaves, lr=lr)
     gen = torch.Generator().manual_seed(int(seed))
     losses = []
@@ -1477,7 +1487,7 @@ def refine_bake(volume, warps, frames, *, steps, lr, batch_rays=None, params=("v
         w = None
         if grids is not None:
             w = dict(warps, warp=grids if grids.dim() == 4 else grids[int(index) if grids.shape[0] > 1 else 0])
-        out = render_baked_train(dict(volume, raw=vol), w, rays, **render)
+        out = render_fn(dict(volume, raw=vol) if sh is None else dict(volume, raw=vol, sh=sh), w, rays, **render)
         loss = ((out["rgb_map"] - target) ** 2).mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -1485,5 +1495,181 @@ def refine_bake(volume, warps, frames, *, steps, lr, batch_rays=None, params=("v
         losses.append(loss.detach())
     history = torch.stack(losses).cpu().tolist() if losses else []
     new_volume = dict(volume, raw=vol.detach().to(volume["raw"].dtype))
+    if sh is not None:
+        new_volume["sh"] = sh.detach().to(volume["sh"].dtype)
     new_warps = None if warps is None else dict(warps, warp=grids.detach().to(warps["warp"].dtype))
     return new_volume, new_warps, history
+
+
+# --------------------------------------------------------------------------------------------
+# view-dependent bakes under autograd (nrnerf_sh_lookup_backward): refine the coefficients of an SH volume on images
+# --------------------------------------------------------------------------------------------
+class _ShLookup(torch.autograd.Function):
+    """``[N, S, 4]`` logits of a view-dependent record at ``points4 [N, S, 4]`` (xyz first).  Forward: the lookup kernel of
+    ``nrnerf_sh_volume_render`` (``points4_in``, no maps, ``raw`` out); backward: ``nrnerf_grid_lookup_backward`` on ``raw`` plus
+    ``nrnerf_sh_lookup_backward`` on ``sh``, the two ``d_points`` added.  ``rays`` given: the RAY rule, None: DIFFERENCES."""
+
+    @staticmethod
+    def forward(ctx, raw, sh, points4, rays, lo, hi, degree):
+        raw, sh, points4 = raw.detach(), sh.detach(), points4.detach()
+        N, S = int(points4.shape[0]), int(points4.shape[1])
+        dev = raw.device
+        record = {"raw": raw, "sh": sh, "sh_degree": degree, "min_point": lo, "max_point": hi}
+        front = rays if rays is not None else torch.zeros((N, 8), dtype=torch.float32, device=dev)       # (read in RAY mode only)
+        if N:
+            out = sh_volume_render(record, front, N_samples=S, points4=points4, composite=False, retraw=True, ray_directions=rays is not None)["raw"]
+        else:
+            out = torch.empty((0, S, 4), dtype=torch.float32, device=dev)
+        ctx.save_for_backward(raw, sh, points4, front)
+        ctx.lo, ctx.hi, ctx.degree, ctx.ray_dirs = lo, hi, degree, rays is not None
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        raw, sh, points4, rays = ctx.saved_tensors
+        want_raw, want_sh, want_points = ctx.needs_input_grad[:3]
+        if g_raw is None or not (want_raw or want_sh or want_points):
+            return (None,) * 7
+        dev = raw.device
+        N, S = int(points4.shape[0]), int(points4.shape[1])
+        g = tuple(int(v) for v in (raw.shape[2], raw.shape[1], raw.shape[0]))
+        g_raw = g_raw.to(dtype=torch.float32).contiguous()
+        f32 = dict(dtype=torch.float32, device=dev)
+        d_raw = torch.zeros(raw.shape, **f32) if want_raw else None
+        d_sh = torch.zeros(sh.shape, **f32) if want_sh else None
+        d_points = torch.zeros((N, S, 4), **f32) if want_points else None
+        if N:
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            xyz_raw = torch.empty((N, S, 3), **f32) if want_points else None
+            xyz_sh = torch.empty((N, S, 3), **f32) if want_points else None
+            d_dirs = torch.empty((N, S, 3), **f32) if want_points and not ctx.ray_dirs else None          # the workspace of the chain
+            with torch.cuda.device(dev):
+                if want_raw or want_points:
+                    a = _lib.GridLookupBackwardArgs()
+                    a.struct_size = C.sizeof(a)
+                    a.grid, a.grid_dtype = raw.data_ptr(), _VOLUME_DTYPES[raw.dtype]
+                    _grid_record_fields(a, ctx.lo, ctx.hi, g)
+                    a.n_points, a.points, a.point_stride, a.g_value = N * S, points4.data_ptr(), 4, g_raw.data_ptr()
+                    a.d_grid = d_raw.data_ptr() if want_raw else None
+                    a.d_points = xyz_raw.data_ptr() if want_points else None
+                    _lib.check(_lib.load().nrnerf_grid_lookup_backward(C.byref(a), stream), "nrnerf_grid_lookup_backward")
+                if want_sh or want_points:
+                    b = _lib.ShLookupBackwardArgs()
+                    b.struct_size = C.sizeof(b)
+                    b.n_rays, b.n_samples = N, S
+                    b.rays, b.ray_stride = rays.data_ptr(), int(rays.shape[1])
+                    b.points4 = points4.data_ptr()
+                    b.direction_mode = _lib.SH_DIRECTION_RAY if ctx.ray_dirs else _lib.SH_DIRECTION_DIFFERENCES
+                    b.sh, b.sh_dtype, b.sh_degree = sh.data_ptr(), _VOLUME_DTYPES[sh.dtype], ctx.degree
+                    _grid_record_fields(b, ctx.lo, ctx.hi, g)
+                    b.g_raw = g_raw.data_ptr()
+                    b.d_sh = d_sh.data_ptr() if want_sh else None
+                    b.d_points = xyz_sh.data_ptr() if want_points else None
+                    b.d_dirs = d_dirs.data_ptr() if d_dirs is not None else None
+                    _lib.check(_lib.load().nrnerf_sh_lookup_backward(C.byref(b), stream), "nrnerf_sh_lookup_backward")
+            if want_points:
+                d_points[..., :3] = xyz_raw + xyz_sh
+        return ((d_raw.to(raw.dtype) if want_raw else None), (d_sh.to(sh.dtype) if want_sh else None), d_points, None, None, None, None)
+
+
+def sh_lookup(volume_record, points, rays=None):
+    """The logits of a view-dependent volume record (``bake(sh_degree=1 or 2)``: ``"raw"`` and ``"sh"``) at the bent points ``points [N, S, 3]`` (or
+    ``[N, S, 4]``, xyz first) of ``N`` rays: ``[N, S, 4]`` float32 -- the colour logits after the spherical-harmonic sum, and sigma -- the bits of
+    ``sh_volume_render(points4=..., composite=False, retraw=True)``, and differentiable with respect to ``volume_record["raw"]``,
+    ``volume_record["sh"]`` and ``points`` (``nrnerf_grid_lookup_backward`` plus ``nrnerf_sh_lookup_backward``).  ``rays [N, >= 8]`` given: every
+    sample's direction is its ray's (RAY; nothing flows from the direction into the points); ``None``: the difference of consecutive points
+    (DIFFERENCES, ``S >= 2``; the chain back to the points is part of the gradient).  Rays carry no gradient.  The gradients of ``raw`` and
+    ``sh`` are summed in float32 with atomic adds -- their last bits can differ between runs -- and cast to the record's dtype once."""
+    if not _has_sh(volume_record):
+        raise R.Unsupported("sh_lookup takes a volume record with spherical-harmonic coefficients (\"sh\"): grid_lookup serves a plain grid")
+    vol, lo, hi, _ = _grid_parts(volume_record, "raw", "volume")
+    _, degree = _sh_parts(volume_record, vol)
+    dev = vol.device
+    if not torch.is_tensor(points) or points.dim() != 3 or points.shape[-1] not in (3, 4):
+        raise ValueError(f"points must be [N, S, 3] or [N, S, 4], got {tuple(points.shape) if torch.is_tensor(points) else type(points)}")
+    N, S = int(points.shape[0]), int(points.shape[1])
+    if not 1 <= S <= _lib.MAX_SAMPLES:
+        raise ValueError(f"1 <= S <= {_lib.MAX_SAMPLES}, got {S}")
+    if rays is None and S < 2:
+        raise ValueError("a direction from the difference of bent points needs 2 samples or more")
+    if rays is not None:
+        if not torch.is_tensor(rays) or rays.dim() != 2 or rays.shape[0] != N or rays.shape[1] < 8:
+            raise ValueError(f"rays must be [{N}, >= 8], got {tuple(rays.shape) if torch.is_tensor(rays) else type(rays)}")
+        rays = rays.detach().to(device=dev, dtype=torch.float32).contiguous()
+    p = points.to(device=dev, dtype=torch.float32)
+    if p.shape[-1] == 3:
+        p = torch.cat([p, torch.zeros_like(p[..., :1])], -1)
+    return _ShLookup.apply(volume_record["raw"].contiguous(), volume_record["sh"].contiguous(), p.contiguous(), rays, lo, hi, degree)
+
+
+def render_sh_train(volume, warp, rays, *, N_samples, z_vals=None, lindisp=False, white_bkgd=False, rigidity_cutoff=None,
+                    test_time_scaling=None, removal_threshold=None):
+    """``render_baked``'s value rule for a view-dependent record under autograd, with respect to ``volume["raw"]``, ``volume["sh"]`` and / or
+    ``warp["warp"]`` (whichever requires a gradient): ``{"rgb_map", "disp_map", "acc_map", "weights"}``, the forward bits of ``render_baked``.
+    ``render_baked_train``'s composition with ``sh_lookup`` in place of the volume's ``grid_lookup``: behind a warp a sample's direction is the
+    difference of the ray's consecutive bent points (DIFFERENCES, 2 samples or more), without one (``warp=None``; the knobs must be ``None``)
+    the ray's own direction (RAY) -- the rule ``sh_volume_render`` follows.  Rays and depths carry no gradient."""
+    from .training import _Composite
+    if not _has_sh(volume):
+        raise R.Unsupported("render_sh_train takes a volume record with \"sh\": render_baked_train serves a plain bake")
+    if not torch.is_tensor(rays) or rays.device.type != "cuda":
+        raise R.Unsupported("rays are not on a ROCm device")
+    _grid_parts(volume, "raw", "volume")
+    dev = volume["raw"].device
+    if warp is not None:
+        _, wlo, whi, _ = _grid_parts(warp, "warp", "warp")
+        if warp["warp"].device != dev:
+            raise ValueError(f"the volume is on {dev}, the warp on {warp['warp'].device}")
+    elif rigidity_cutoff is not None or test_time_scaling is not None or removal_threshold is not None:
+        raise ValueError("the bender's knobs need a warp")
+    if rays.dim() != 2 or rays.shape[1] < 8:
+        raise ValueError(f"rays must be [N, >= 8], got {tuple(rays.shape)}")
+    f32 = dict(dtype=torch.float32, device=dev)
+    rays = rays.detach().to(**f32).contiguous()
+    N, S = int(rays.shape[0]), int(z_vals.shape[1] if z_vals is not None else N_samples)
+    if not 1 <= S <= _lib.MAX_SAMPLES:
+        raise ValueError(f"1 <= N_samples <= {_lib.MAX_SAMPLES}, got {S}")
+    if warp is not None and S < 2:
+        raise ValueError("a direction from the difference of bent points needs 2 samples or more")
+    with torch.no_grad():
+        pts = None
+        if z_vals is not None:
+            if tuple(z_vals.shape) != (N, S):
+                raise ValueError(f"z_vals must be {(N, S)}, got {tuple(z_vals.shape)}")
+            z = z_vals.detach().to(**f32).contiguous()
+        elif S >= 2:
+            z, pts = sample_rays(rays, S, lindisp)
+        else:       # one sample: the near bound
+            z = (1.0 / (1.0 / rays[:, 6:7])).contiguous() if lindisp else rays[:, 6:7].contiguous()
+        if pts is None:
+            pts = rays[:, None, 0:3] + rays[:, None, 3:6] * z[..., None]                # a product and a sum, each rounded, as the kernels'
+    if warp is not None:
+        um = grid_lookup(warp["warp"], wlo, whi, pts)
+        u, m = um[..., :3], um[..., 3]
+        if rigidity_cutoff is not None:
+            m = torch.where(m.detach() <= torch.tensor(float(rigidity_cutoff), **f32), torch.zeros_like(m), m)      # rnh:563-564
+        off = m[..., None] * u                                                                                        # rnh:567
+        if test_time_scaling is not None:
+            off = off * torch.tensor(float(test_time_scaling), **f32)                                                 # rnh:568-569
+        raw = sh_lookup(volume, pts + off)
+    else:
+        raw = sh_lookup(volume, pts, rays)
+    if removal_threshold is not None:
+        kill = m.detach() >= torch.tensor(float(removal_threshold), **f32)                                            # rnh:308-311
+        raw = torch.cat([raw[..., :3], torch.where(kill, raw[..., 3] * 0.0, raw[..., 3])[..., None]], -1)
+    rgb, disp, acc, weights = _Composite.apply(raw, rays, z, None, bool(white_bkgd), 0, None)[:4]
+    return {"rgb_map": rgb, "disp_map": disp, "acc_map": acc, "weights": weights}
+
+
+def refine_sh_bake(volume, warps, frames, *, steps, lr, batch_rays=None, params=("volume", "sh"), optimizer="adam", seed=0, **render):
+    """``refine_bake`` for a view-dependent bake: ``steps`` iterations of Adam (``optimizer="sgd"``: plain gradient descent) at rate ``lr`` on the
+    mean squared error of ``render_sh_train``'s ``rgb_map`` against target colours.  ``frames``, ``warps``, ``batch_rays``, ``seed`` and ``render``:
+    ``refine_bake``'s.  ``params``: a subset of ``"volume"`` (the record's ``"raw"``), ``"sh"`` (its coefficients) and ``"warp"``; the refined
+    grids are kept in float32 during the loop and come back in their records' dtype.  Returns ``(volume record, warps record or None, [loss
+    per step])``; the inputs are not modified."""
+    if not _has_sh(volume):
+        raise R.Unsupported("refine_sh_bake takes a volume record with \"sh\": refine_bake serves a plain bake")
+    _sh_parts(volume, _grid_parts(volume, "raw", "volume")[0])
+    return _refine_loop(volume, warps, frames, steps, lr, batch_rays, tuple(params), ("volume", "sh", "warp"), optimizer, seed, render_sh_train,
+                        render, "refine_sh_bake")
