@@ -237,72 +237,10 @@ def test_damaged_emulations_are_rejected():
 
 # ---- the generic kernels' operands: the module's weights rounded with torch ARE what the width-class image holds --------------------
 def width_class_image_operands(coarse, fine, cfg):
-    """The weight matrices and biases in the width-class trunk image (nrnerf_pack_host which = 12, bf16), read fragment by fragment in the
-    order tests/test_packing.py::test_width_class_stream_reproduces_any_plain_trunk consumes it: a fragment is W[16 rows][32 positions], lane
-    (r, g) holding positions 8 g .. 8 g + 7; tiles in pairs with their k-steps interleaved, every layer padded to whole 4-unit ring periods;
-    encoding k-steps f16 (positions 0..2 identity, 3 none, then (sin, cos) pairs), hidden k-step s position 8 g + e = feature 32 s + 4 g + e
-    (e < 4) or 32 s + 16 + 4 g + e - 4."""
-    info, stream, bias = T._pack_image(coarse, fine, "bf16", 12)
-    W, D, L = cfg.netwidth, cfg.netdepth, cfg.multires
+    """The weight matrices and biases in the width-class trunk image (nrnerf_pack_host which = 12, bf16), read fragment by fragment
+    (trunk_reference.frag16_image_operands, layout "gx")."""
     skip = cfg.skips[0] if cfg.skips else -1
-    WC = (W + 63) // 64 * 64
-    n_enc = 3 + 6 * L
-    as_bf16 = (stream.view(np.uint16).astype(np.uint32) << 16).view(np.float32).astype(np.float64)
-    as_f16 = stream.view(np.float16).astype(np.float64)
-    pos, tile = [0], [0]
-
-    def enc_col(q):
-        if q < 3:
-            return q
-        if q == 3:
-            return -1
-        m, b = (q - 4) // 2, (q - 4) & 1
-        return 3 + 6 * (m // 3) + 3 * b + (m % 3) if m < 3 * L else -1
-
-    def hid_col(q):
-        s, g, e = q // 32, (q % 32) // 8, q % 8
-        return 32 * s + 4 * g + e if e < 4 else 32 * s + 16 + 4 * g + e - 4
-
-    def layer(nt, n_enc_steps, n_hid_steps):
-        """-> W [16 nt, n_enc (if any) + WC (if any)], bias [16 nt]"""
-        start, ns = pos[0], n_enc_steps + n_hid_steps
-        out = np.zeros((16 * nt, (n_enc if n_enc_steps else 0) + (WC if n_hid_steps else 0)))
-
-        def take(t, s):
-            f16 = s < n_enc_steps
-            f = (as_f16 if f16 else as_bf16)[pos[0] * 512:(pos[0] + 1) * 512].reshape(64, 8)
-            pos[0] += 1
-            for lane in range(64):
-                for e in range(8):
-                    q = 8 * (lane >> 4) + e
-                    if f16:
-                        c = enc_col(32 * s + q)
-                    else:
-                        c = (n_enc if n_enc_steps else 0) + hid_col(32 * (s - n_enc_steps) + q)
-                    if c >= 0:
-                        out[16 * t + (lane & 15), c] = f[lane, e]
-                    else:
-                        assert f[lane, e] == 0.0
-        for p_ in range(0, nt - 1, 2):
-            for s in range(ns):
-                take(p_, s)
-                take(p_ + 1, s)
-        if nt & 1:
-            for s in range(ns):
-                take(nt - 1, s)
-        b = bias[tile[0] * 16:(tile[0] + nt) * 16].astype(np.float64)
-        tile[0] += nt
-        units = -(-(pos[0] - start) // 16)
-        pos[0] = start + (-(-units // 4) * 4) * 16
-        return torch.from_numpy(out), torch.from_numpy(b)
-
-    NT = WC // 16
-    layers = [layer(NT, 2, 0)]
-    for i in range(1, D):
-        layers.append(layer(NT, 2 if i - 1 == skip else 0, WC // 32))
-    head = layer(1, 0, WC // 32)
-    assert tile[0] == info.n_bias_tiles
-    return layers, head
+    return T.frag16_image_operands(T._pack_image(coarse, fine, "bf16", 12), "bf16", cfg.netwidth, cfg.netdepth, cfg.multires, skip, "gx")
 
 
 @pytest.mark.parametrize("cfg_kw", [dict(netdepth=6, netwidth=192, skips=(2,)), dict(netdepth=3, netwidth=64, skips=())], ids=["d6_w192", "d3_w64_no_skip"])

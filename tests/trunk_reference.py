@@ -100,18 +100,22 @@ def sincos_error_bound(x, L):
     return torch.cat(cols, -1)
 
 
-def encoding_operand(x, L, sixteen_bit):
+def encoding_operand(x, L, sixteen_bit, clamp=True):
     """The operand the reference multiplies by -- f16(enc64), enc64 the float64 encoding of the fp32 3-vectors x -- and how far the kernel's
     may be from it, per element.  16-bit modes: the kernel's sin / cos is an fp32 value hw within eps = sincos_error_bound of enc64, rounded to
     f16; rounding is monotone, so its operand lies in [f16(enc64 - eps), f16(enc64 + eps)]: where both ends ARE the reference's operand the
     allowance is zero, else the distance to the farther end -- never more than the issue's UH |e| + EPS_SC.  The identity columns are f16 of
     the same fp32 value on both sides: zero (the issue allows one f16 neighbour).  fp32 mode: sincosf of the exact fp32 product,
-    4 U32 max(|e|, 1); the identity columns are exact."""
+    4 U32 max(|e|, 1); the identity columns are exact.  clamp=False leaves the issue's figure out: it is half an f16 ulp of e plus EPS_SC, and
+    where the two roundings differ they differ by a WHOLE ulp -- more than that figure for |e| in the lower part of a binade -- so a bound
+    that must hold for every element (tests/inference_reference.py interval_bound) takes the distance to the farther end as it is."""
     e64 = encoding64(x, L)
     if sixteen_bit:
         f16 = lambda t: t.to(torch.float32).to(torch.float16).double()
         op, eps = f16(e64), sincos_error_bound(x, L)
-        delta = torch.maximum(f16(e64 + eps) - op, op - f16(e64 - eps)).clamp_max(UH * e64.abs() + EPS_SC)
+        delta = torch.maximum(f16(e64 + eps) - op, op - f16(e64 - eps))
+        if clamp:
+            delta = delta.clamp_max(UH * e64.abs() + EPS_SC)
         delta[..., :3] = 0.0
     else:
         op = e64.to(torch.float32).double()
@@ -203,7 +207,7 @@ def enc_slot_col(L, hh, q):
     return 3 + 6 * (hh * F0 + fl) + 3 * fn + c if (fl < F0 and hh * F0 + fl < L) else -1
 
 
-def _pack_image(coarse, fine, precision, which):
+def _pack_image(coarse, fine, precision, which, with_units=False):
     from nonrigid_nerf_amd import _lib
     from nonrigid_nerf_amd.render import build_model_desc
     desc, keep = build_model_desc(coarse, fine, precision, 0)
@@ -215,7 +219,7 @@ def _pack_image(coarse, fine, precision, which):
     bias = np.zeros(info.n_bias_tiles * 32, dtype=np.float32)
     _lib.check(lib.nrnerf_pack_host(C.byref(desc), which, C.byref(info), stream.ctypes.data_as(C.c_void_p), stream.nbytes,
                                     units.ctypes.data_as(C.POINTER(C.c_uint32)), bias.ctypes.data_as(C.POINTER(C.c_float))), "pack")
-    return info, stream, bias
+    return (info, stream, bias, units) if with_units else (info, stream, bias)
 
 
 class _Prober:
@@ -318,26 +322,20 @@ class CompiledOperands:
     LV: int
 
 
-def compiled_operands(scene, which, precision):
-    """The operand weights of nrnerf_trunk_forward / _backward for ``scene``'s coarse (which = 0) or fine (1) network, from the packed
-    images (nrnerf_pack_host which = 0 | 1 forward, 4 | 5 backward-data) of the same networks WITHOUT the ray bender: the trunk-only image
-    the training kernels stream (tests/test_packing.py: the split images are the two halves of the fused stream, byte for byte)."""
-    from nonrigid_nerf_amd.synthetic import Scene, build_modules
-    cfg = scene.cfg
-    _, coarse, fine = build_modules(Scene(cfg, None, scene.coarse, scene.fine))
-    views, tcb = cfg.use_viewdirs, cfg.time_conditioned_baseline
-    fcfg = cfg.for_fine() if which == 1 else cfg
-    Wd, D, L, LV, skip = fcfg.netwidth, fcfg.netdepth, cfg.multires, cfg.multires_views, cfg.skips[0]
-    NT, n_enc = Wd // 32, 3 + 6 * cfg.multires
-    lat = [("vec16", cfg.latent_size)] if tcb else []
+def probe_forward_image(image, precision, D, Wd, L, LV, skip, views, latent=0):
+    """The forward layers of a 32x32 trunk image (nrnerf_pack_host which = 0 | 1, or 2: the trunk half of a split image), probed layer by
+    layer: (W [D], b [D], head | None, alpha, views (the FOLDED layer, columns [direction encoding | hidden]), rgb | None), float64.
+    latent > 0 (time-conditioned baseline): the latent columns behind the encoding are probed and left out."""
+    NT, n_enc = Wd // 32, 3 + 6 * L
+    lat = [("vec16", latent)] if latent else []
     t64 = lambda a: torch.from_numpy(np.ascontiguousarray(a)).double()
-    pr = _Prober(*_pack_image(coarse, fine, precision, which), precision)
+    pr = _Prober(*image, precision)
     Ws, bs = [], []
     for i in range(D):
         groups = ([("enc", L)] + lat if (i == 0 or i - 1 == skip) else []) + ([("hid", Wd)] if i > 0 else [])
         Wm, b = pr.layer(NT, groups)
-        if tcb and (i == 0 or i - 1 == skip):        # the latent columns reach the training kernels through ray_bias
-            Wm = np.concatenate([Wm[:, :n_enc], Wm[:, n_enc + cfg.latent_size:]], 1)
+        if latent and (i == 0 or i - 1 == skip):     # the latent columns reach the training kernels through ray_bias
+            Wm = np.concatenate([Wm[:, :n_enc], Wm[:, n_enc + latent:]], 1)
         Ws.append(t64(Wm)); bs.append(t64(b))
     head = alpha = vw = rgb = None
     if views:
@@ -352,6 +350,132 @@ def compiled_operands(scene, which, precision):
         rows = [0, 1, 2, 3, 8]                    # accumulator registers 0..4 of the lower lane half (tile_row(r, 0))
         head = (t64(Wm[rows]), t64(b[rows]))
     pr.done()
+    return Ws, bs, head, alpha, vw, rgb
+
+
+def frag16_image_operands(image, precision, W, D, L, skip, layout):
+    """The weight matrices and biases of a plain-headed trunk image of the 16x16x32 kernels, read fragment by fragment in the order
+    tests/test_packing.py consumes them (test_x16_stream_reproduces_the_trunk, test_width_class_stream_reproduces_any_plain_trunk): a fragment
+    is W[16 rows][32 positions], lane (r, g) holding positions 8 g .. 8 g + 7; tiles in pairs with their k-steps interleaved, an odd last tile
+    alone; encoding k-steps f16, hidden k-step s position 8 g + e = feature 32 s + 4 g + e (e < 4) or 32 s + 16 + 4 g + e - 4.
+    layout "gx" (nrnerf_pack_host which = 11 | 12, csrc/nrnerf_gx16.h): the width padded to a multiple of 64, every layer padded to whole
+    4-unit ring periods, encoding positions [x, y, z, -, (sin, cos) pairs]; layout "x16" (which = 10, csrc/nrnerf_net_x16.h): the layers back
+    to back, the encoding in the slots of nrnerf_plan.h x16_enc_col.  -> ([(W [16 nt, n_enc (if read) + WC], bias [16 nt])] per layer, head)."""
+    info, stream, bias = image[:3]
+    gx = layout == "gx"
+    WC = (W + 63) // 64 * 64 if gx else W
+    n_enc = 3 + 6 * L
+    as_bf16 = (stream.view(np.uint16).astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+    as_f16 = stream.view(np.float16).astype(np.float64)
+    pos, tile = [0], [0]
+    if gx:
+        def enc_col(q):
+            if q < 3:
+                return q
+            if q == 3:
+                return -1
+            m, b = (q - 4) // 2, (q - 4) & 1
+            return 3 + 6 * (m // 3) + 3 * b + (m % 3) if m < 3 * L else -1
+    else:
+        from tests.test_packing import _x16_enc_col
+        enc_col = lambda q: _x16_enc_col(L, q // 32, (q % 32) // 8, q % 8)
+
+    def hid_col(q):
+        s, g, e = q // 32, (q % 32) // 8, q % 8
+        return 32 * s + 4 * g + e if e < 4 else 32 * s + 16 + 4 * g + e - 4
+    enc_cols = [enc_col(q) for q in range(64)]
+    hid_cols = [hid_col(q) for q in range(WC)]
+
+    def layer(nt, n_enc_steps, n_hid_steps):
+        start, ns = pos[0], n_enc_steps + n_hid_steps
+        lead = n_enc if n_enc_steps else 0
+        out = np.zeros((16 * nt, lead + (WC if n_hid_steps else 0)))
+
+        def take(t, s):
+            f16 = s < n_enc_steps
+            f = (as_f16 if (f16 or precision == "f16") else as_bf16)[pos[0] * 512:(pos[0] + 1) * 512].reshape(64, 8)
+            pos[0] += 1
+            for g in range(4):
+                for e in range(8):
+                    c = enc_cols[32 * s + 8 * g + e] if f16 else lead + hid_cols[32 * (s - n_enc_steps) + 8 * g + e]
+                    col = f[16 * g:16 * g + 16, e]
+                    if c >= 0:
+                        out[16 * t:16 * t + 16, c] = col
+                    else:
+                        assert not col.any(), "a position without a column carries no weight"
+        for p_ in range(0, nt - 1, 2):
+            for s in range(ns):
+                take(p_, s)
+                take(p_ + 1, s)
+        if nt & 1:
+            for s in range(ns):
+                take(nt - 1, s)
+        b = bias[tile[0] * 16:(tile[0] + nt) * 16].astype(np.float64)
+        tile[0] += nt
+        if gx:
+            units = -(-(pos[0] - start) // 16)
+            pos[0] = start + (-(-units // 4) * 4) * 16
+        return torch.from_numpy(out), torch.from_numpy(b)
+
+    NT = WC // 16
+    layers = [layer(NT, 2, 0)]
+    for i in range(1, D):
+        layers.append(layer(NT, 2 if i - 1 == skip else 0, WC // 32))
+    head = layer(1, 0, WC // 32)
+    assert tile[0] == info.n_bias_tiles, "the image holds other layers than were read"
+    if not gx:
+        assert pos[0] * 1024 <= info.stream_bytes and not stream[pos[0] * 1024:].any(), "the stream goes on behind the head"
+    return layers, head
+
+
+def generic_program_operands(image, precision):
+    """The layers of a run-time-parameterised kernel's program (nrnerf_pack_host which = 7 | 8, csrc/nrnerf_generic.h), decoded as
+    tests/test_packing.py::_run_generic_program walks them: per layer dict(W = {source buffer: [32 nt, positions]}, b [32 nt], relu, dst,
+    o_col, o_rows); buffers 0 = E (the encoding in reference column order [, latent]), 1 = H (hidden), 2 = V (direction encoding); fragments
+    against E / V are f16.  16-bit modes only."""
+    from tests.test_packing import tile_row
+    info, stream, bias, units = image
+    assert info.frag_bytes == 1024 and precision in ("bf16", "f16")
+    u = units.astype(np.int64)
+    n_layers = int(u[0])
+    prog = u[1:1 + 11 * n_layers].reshape(n_layers, 11)
+    raw16 = stream.view(np.uint16)
+    rows = np.array([tile_row(r, h) for h in range(2) for r in range(16)])
+    out = []
+    for (w_frag, bias_tile, nt, src0, ns0, src1, ns1, dst, relu, o_col, o_rows) in prog:
+        ns = int(ns0 + ns1)
+        mats = {}
+        b = np.zeros(32 * nt)
+        for t in range(int(nt)):
+            b[32 * t + rows] = bias[(bias_tile + t) * 32:(bias_tile + t) * 32 + 32]
+            for sl in range(ns):
+                src, s = (int(src0), sl) if sl < ns0 else (int(src1), sl - int(ns0))
+                fi = int(w_frag) + t * ns + sl
+                bits = raw16[fi * 512:(fi + 1) * 512].reshape(64, 8)
+                as_f16 = precision == "f16" or src != 1
+                fr = bits.view(np.float16).astype(np.float64) if as_f16 else (bits.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
+                M = mats.setdefault(src, np.zeros((32 * int(nt), 16 * int(ns0 if sl < ns0 else ns1))))
+                for h in range(2):
+                    M[32 * t:32 * t + 32, 16 * s + 8 * h:16 * s + 8 * h + 8] = fr[32 * h:32 * h + 32]
+        out.append(dict(W={k: torch.from_numpy(v) for k, v in mats.items()}, b=torch.from_numpy(b), relu=bool(relu), dst=int(dst),
+                        o_col=int(o_col), o_rows=int(o_rows)))
+    return out
+
+
+def compiled_operands(scene, which, precision):
+    """The operand weights of nrnerf_trunk_forward / _backward for ``scene``'s coarse (which = 0) or fine (1) network, from the packed
+    images (nrnerf_pack_host which = 0 | 1 forward, 4 | 5 backward-data) of the same networks WITHOUT the ray bender: the trunk-only image
+    the training kernels stream (tests/test_packing.py: the split images are the two halves of the fused stream, byte for byte)."""
+    from nonrigid_nerf_amd.synthetic import Scene, build_modules
+    cfg = scene.cfg
+    _, coarse, fine = build_modules(Scene(cfg, None, scene.coarse, scene.fine))
+    views, tcb = cfg.use_viewdirs, cfg.time_conditioned_baseline
+    fcfg = cfg.for_fine() if which == 1 else cfg
+    Wd, D, L, LV, skip = fcfg.netwidth, fcfg.netdepth, cfg.multires, cfg.multires_views, cfg.skips[0]
+    NT, n_enc = Wd // 32, 3 + 6 * cfg.multires
+    t64 = lambda a: torch.from_numpy(np.ascontiguousarray(a)).double()
+    Ws, bs, head, alpha, vw, rgb = probe_forward_image(_pack_image(coarse, fine, precision, which), precision, D, Wd, L, LV, skip, views,
+                                                       cfg.latent_size if tcb else 0)
     # backward-data: head^T (view-dependent: rgb_linear^T, then the joined layer), pts_linears[D-1 .. 1]^T, pts_linears[0]^T
     if tcb:
         # nrnerf_pack_host hands out no backward image of the time-conditioned baseline: its transposed weights by the rule the other
@@ -391,8 +515,11 @@ def round_to(x, dtype):
 def module_operands(net, sixteen_bit):
     """The operand weights of a non-compiled trunk from the module's own weights rounded with torch: bf16, and f16 in the columns that meet
     an encoding (layer 0, the encoding columns of the layer behind the skip, the direction columns of the views layer); fp32 mode: as
-    they are.  Returns (W [depth], b [depth], extra) with extra = dict of the head's layers (output | alpha, feature, views, rgb)."""
-    wdt = (lambda w: round_to(w, torch.bfloat16)) if sixteen_bit else (lambda w: w.detach().double())
+    they are.  Returns (W [depth], b [depth], extra) with extra = dict of the head's layers (output | alpha, feature, views, rgb).
+    ``sixteen_bit`` may also name the precision: "f16" rounds every weight to f16 (the inference kernels' second 16-bit mode)."""
+    hdt = torch.float16 if sixteen_bit == "f16" else torch.bfloat16
+    sixteen_bit = sixteen_bit not in (False, "f32")
+    wdt = (lambda w: round_to(w, hdt)) if sixteen_bit else (lambda w: w.detach().double())
     edt = (lambda w: round_to(w, torch.float16)) if sixteen_bit else (lambda w: w.detach().double())
     n_enc = int(net.input_ch)
     skips = [int(k) for k in net.skips]
