@@ -1453,6 +1453,71 @@ typedef struct nrnerf_culled_volume_render_args {
 } nrnerf_culled_volume_render_args;
 int nrnerf_culled_volume_render(const nrnerf_culled_volume_render_args* args, void* hip_stream);
 
+/* ---- ABI 10 (additions): hierarchical sampling of a baked scene -- coarse pass, sample_pdf, fine pass in one kernel.
+ *
+ * The network path places n_importance more samples where the coarse pass' weights are (sample_pdf, run_nerf_helpers.py:651-698; the merge,
+ * train.py:910-920).  nrnerf_hierarchical_volume_render does that for a baked scene without a round trip through memory: per ray the coarse
+ * pass' logits stay in registers, the merged depths in the wave's LDS (csrc/nrnerf_hier_volume.hip).
+ *
+ * THE VALUE RULE is the composition of three calls above, bit for bit:
+ *   (A) nrnerf_warped_volume_render at n_samples with this record's rays, z, lindisp, grids, knobs and white_bkgd, `raw` written;
+ *   (B) nrnerf_composite_forward on that raw with the same rays, z, lindisp and white_bkgd, n_importance and u as given here;
+ *   (C) nrnerf_warped_volume_render at n_samples + n_importance with z = (B)'s z_merged, the same grids, knobs and white_bkgd.
+ * rgb0 / disp0 / acc0 are (A)'s rgb / disp / acc; z_std and z_vals are (B)'s z_std and z_merged; every other output is (C)'s output of the same
+ * name.  u [N, n_importance] are the uniforms of sample_pdf, NULL: linspace(0, 1, n_importance) (det = True).
+ * warp == NULL is allowed: (u, m) = 0 at every sample, straight rays -- the rule of a point outside the warp's box, hence the bits of an
+ * all-zero warp (warp_dtype, warp_g and the warp's box are then not read).
+ * One kernel, no workspace, no atomics, no device counter: the same bits on every run.  Device pointers only, asynchronous on the stream,
+ * allocates nothing; runs on the device that owns rgb.
+ * Checks, in this order: NRNERF_ERR_INVALID for a NULL record or a wrong struct_size; n_rays < 0, n_samples < 3 (the pdf over weights[1:-1] is
+ * 0 / 0 below), n_importance < 1, ray_stride < 8; the volume's g < 2, max_c not > min_c (NaN included), unknown volume_dtype; with a warp, the
+ * same three of the warp.  NRNERF_ERR_UNSUPPORTED for n_samples > 256 or n_samples + n_importance > 512 (the composition of the three calls
+ * serves those, up to NRNERF_MAX_SAMPLES); more than 2^30 vertices in either grid; 2^31 or more samples.  Then n_rays == 0 answers NRNERF_OK
+ * without a launch.  Then NRNERF_ERR_INVALID for a NULL rays / volume; rgb, disp, acc not all given; rgb0, disp0, acc0 neither all given nor
+ * all NULL; and -- the first HIP calls -- memory that is not device memory of one device, a raw / points4 that is not 16-byte aligned, a grid
+ * that is not aligned to one vertex. */
+typedef struct nrnerf_hierarchical_volume_render_args {
+    uint32_t struct_size;       /* sizeof(nrnerf_hierarchical_volume_render_args) */
+    int32_t n_rays;             /* N >= 0 */
+    int32_t n_samples;          /* S_c: 3 .. 256 */
+    int32_t n_importance;       /* I >= 1, S_c + I <= 512 */
+    const float* rays;          /* [N, ray_stride]: o (0..2), d (3..5), near, far (6, 7) */
+    int32_t ray_stride;         /* >= 8 */
+    int32_t lindisp;            /* the coarse spacing linear in inverse depth; read when z is NULL */
+    const float* z;             /* [N, S_c] the coarse depths, or NULL: the coarse spacing */
+    const float* u;             /* [N, I] the uniforms of sample_pdf, or NULL: linspace(0, 1, I) */
+    const void* volume;         /* [gz, gy, gx, 4] canonical logits, float32 or half */
+    int32_t volume_dtype;
+    int32_t g[3];
+    float min_point[3];
+    float max_point[3];
+    const void* warp;           /* [wgz, wgy, wgx, 4] (unmasked offset xyz, rigidity mask), float32 or half, or NULL: straight rays */
+    int32_t warp_dtype;
+    int32_t warp_g[3];
+    float warp_min_point[3];
+    float warp_max_point[3];
+    int32_t has_rigidity_cutoff;    float rigidity_cutoff;
+    int32_t has_test_time_scaling;  float test_time_scaling;
+    int32_t white_bkgd;
+    int32_t has_removal_threshold; float removal_threshold;
+    float* rgb;                 /* out [N, 3] the fine pass' maps, all three required */
+    float* disp;                /* out [N] */
+    float* acc;                 /* out [N] */
+    float* rgb0;                /* out [N, 3] the coarse pass' maps: all three or none */
+    float* disp0;               /* out [N] or NULL */
+    float* acc0;                /* out [N] or NULL */
+    float* z_std;               /* out [N] population std of the importance depths, or NULL */
+    float* z_vals;              /* out [N, S_c + I] the merged depths, or NULL */
+    float* raw;                 /* out [N, S_c + I, 4] the fine pass' logits (after the removal knob), 16-byte aligned, or NULL */
+    float* weights;             /* out [N, S_c + I] or NULL */
+    float* alpha;               /* out [N, S_c + I] or NULL */
+    float* surface_pts;         /* out [N, 3] or NULL */
+    float* surface_rigidity;    /* out [N] or NULL */
+    int32_t* median_index;      /* out [N] or NULL */
+    float* points4;             /* out [N, S_c + I, 4] (bent xyz, rigidity after the cutoff), 16-byte aligned, or NULL */
+} nrnerf_hierarchical_volume_render_args;
+int nrnerf_hierarchical_volume_render(const nrnerf_hierarchical_volume_render_args* args, void* hip_stream);
+
 /* Host-only packing (no device needed): writes the MFMA-fragment weight stream + unit table + bias
  * table of one pass exactly as nrnerf_model_create uploads them.  which: 0 = coarse, 1 = fine, 2 = fine without the
  * bender layers, 3 = bender + rigidity layers alone (2, 3: the split-bender path; need a bender and not the exact view directions),

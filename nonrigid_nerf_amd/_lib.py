@@ -415,6 +415,28 @@ class CulledVolumeRenderArgs(C.Structure):
 OCCUPANCY_MIN_LOG2_BLOCK, OCCUPANCY_MAX_LOG2_BLOCK = 1, 4
 
 
+class HierarchicalVolumeRenderArgs(C.Structure):
+    """nrnerf_hierarchical_volume_render_args (ABI 10 additions): coarse pass, sample_pdf + merge and fine pass of a baked scene in one kernel;
+    ``warp`` NULL: straight rays."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_rays", C.c_int32), ("n_samples", C.c_int32), ("n_importance", C.c_int32),
+                ("rays", C.c_void_p), ("ray_stride", C.c_int32), ("lindisp", C.c_int32), ("z", C.c_void_p), ("u", C.c_void_p),
+                ("volume", C.c_void_p), ("volume_dtype", C.c_int32), ("g", C.c_int32 * 3),
+                ("min_point", C.c_float * 3), ("max_point", C.c_float * 3),
+                ("warp", C.c_void_p), ("warp_dtype", C.c_int32), ("warp_g", C.c_int32 * 3),
+                ("warp_min_point", C.c_float * 3), ("warp_max_point", C.c_float * 3),
+                ("has_rigidity_cutoff", C.c_int32), ("rigidity_cutoff", C.c_float),
+                ("has_test_time_scaling", C.c_int32), ("test_time_scaling", C.c_float),
+                ("white_bkgd", C.c_int32), ("has_removal_threshold", C.c_int32), ("removal_threshold", C.c_float),
+                ("rgb", C.c_void_p), ("disp", C.c_void_p), ("acc", C.c_void_p),
+                ("rgb0", C.c_void_p), ("disp0", C.c_void_p), ("acc0", C.c_void_p), ("z_std", C.c_void_p), ("z_vals", C.c_void_p),
+                ("raw", C.c_void_p), ("weights", C.c_void_p), ("alpha", C.c_void_p),
+                ("surface_pts", C.c_void_p), ("surface_rigidity", C.c_void_p), ("median_index", C.c_void_p),
+                ("points4", C.c_void_p)]
+
+
+HIER_MAX_COARSE, HIER_MAX_MERGED = 256, 512     # the fused kernel's bounds on N_samples and N_samples + N_importance (csrc/nrnerf_hier_volume.h)
+
+
 def occupancy_blocks(g: int, log2_block: int) -> int:
     """Blocks per axis of ``g`` vertices (``g - 1`` cells) at ``2 ** log2_block`` cells per block (include/nrnerf.h, "occupancy masks")."""
     return (g - 1 + (1 << log2_block) - 1) >> log2_block
@@ -515,6 +537,7 @@ EXPORTS = {
     "nrnerf_occupancy_words": (C.c_int64, [C.POINTER(C.c_int32), C.c_int32]),
     "nrnerf_occupancy_build": (C.c_int, [C.POINTER(OccupancyBuildArgs), C.c_void_p]),
     "nrnerf_culled_volume_render": (C.c_int, [C.POINTER(CulledVolumeRenderArgs), C.c_void_p]),
+    "nrnerf_hierarchical_volume_render": (C.c_int, [C.POINTER(HierarchicalVolumeRenderArgs), C.c_void_p]),
     "nrnerf_bend_points_workspace_bytes": (C.c_size_t, [C.c_void_p]),
     "nrnerf_bend_points": (C.c_int, [C.c_void_p, C.POINTER(BendPointsArgs), C.c_void_p]),
     "nrnerf_generate_rays": (C.c_int, [C.POINTER(Camera), C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -280,9 +280,13 @@ __device__ __forceinline__ void ray_phase_sync() {
     }
 }
 
-template <int EPL, bool WAVE_LOCAL>
+// LDS_SINK (the fused hierarchical baked render, nrnerf_hier_volume.hip): the merged depths go to `s_sorted` [S + I], an LDS area of this wave
+// that may lie over s_cdf / s_bins (both are dead once the importance depths are drawn) but not over s_z, and to a.z_out only where that is
+// given; no split-bender outputs.  false: the text every earlier caller has had, instantiated to the same device code.
+template <int EPL, bool WAVE_LOCAL, bool LDS_SINK = false>
 __device__ __forceinline__ void sample_merge_ray(const CompositeArgs& a, const int ray, const bool ray_ok, const int lane,
-                                                 const float (&z)[EPL + 1], const float (&w)[EPL], float* s_cdf, float* s_bins, float* s_z) {
+                                                 const float (&z)[EPL + 1], const float (&w)[EPL], float* s_cdf, float* s_bins, float* s_z,
+                                                 float* s_sorted = nullptr) {
     const int S = a.S, I = a.n_importance;
     const int nb = S - 1;          // bins = mid-points; cdf has nb entries (run_nerf_helpers.py:657-659)
     // ---- pdf / cdf over weights[1:-1] + 1e-5 (rnh:654-659)
@@ -370,7 +374,12 @@ __device__ __forceinline__ void sample_merge_ray(const CompositeArgs& a, const i
                 while (lo < hi) { const int mid = (lo + hi) >> 1; if (s_z[mid] <= mine) lo = mid + 1; else hi = mid; }
                 rank = (idx - S) + lo;
             }
-            if (ray_ok) { gmem(a.z_out)[(size_t)ray * n + rank] = mine; split_out(idx, rank, mine); }
+            if constexpr (LDS_SINK) {
+                s_sorted[rank] = mine;
+                if (ray_ok && a.z_out) gmem(a.z_out)[(size_t)ray * n + rank] = mine;
+            } else {
+                if (ray_ok) { gmem(a.z_out)[(size_t)ray * n + rank] = mine; split_out(idx, rank, mine); }
+            }
         }
     } else {
         for (int idx = lane; idx < n; idx += 64) {
@@ -380,7 +389,12 @@ __device__ __forceinline__ void sample_merge_ray(const CompositeArgs& a, const i
                 const float o = s_z[jj];
                 rank += (o < mine || (o == mine && jj < idx)) ? 1 : 0;
             }
-            if (ray_ok) { gmem(a.z_out)[(size_t)ray * n + rank] = mine; split_out(idx, rank, mine); }
+            if constexpr (LDS_SINK) {
+                s_sorted[rank] = mine;
+                if (ray_ok && a.z_out) gmem(a.z_out)[(size_t)ray * n + rank] = mine;
+            } else {
+                if (ray_ok) { gmem(a.z_out)[(size_t)ray * n + rank] = mine; split_out(idx, rank, mine); }
+            }
         }
     }
 }

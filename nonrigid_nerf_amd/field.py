@@ -821,7 +821,7 @@ def sample_rays(rays, N_samples, lindisp=False):
 
 
 def render_volume(volume, rays, *, network=None, latents=None, N_samples=192, z_vals=None, lindisp=False, white_bkgd=False, surface=False,
-                  retraw=False, removal_threshold=None, precision=None, occupancy=None):
+                  retraw=False, removal_threshold=None, precision=None, occupancy=None, N_importance=0, importance_u=None, fused=None):
     """A baked volume rendered along ``rays [N, >= 8]``: ``rgb_map / disp_map / acc_map`` (+ ``raw`` under ``retraw``; ``surface_pts``,
     ``surface_rigidity``, ``median_index`` under ``surface``), no trunk pass.
 
@@ -834,9 +834,16 @@ def render_volume(volume, rays, *, network=None, latents=None, N_samples=192, z_
     A volume record with ``"sh"`` (``bake(sh_degree=1 or 2)`` of a view-dependent head) goes through ``sh_volume_render`` instead: the colour
     of a sample is evaluated at its direction -- the difference of consecutive bent points behind a bender, the ray's direction without.
     ``occupancy``: the volume's mask (``build_occupancy``) -- samples in empty blocks request nothing, through ``culled_volume_render``; ``None``
-    takes the calls above."""
+    takes the calls above.
+    ``N_importance > 0`` (without ``network``: the real bender between the two passes is ``Unsupported``): hierarchical sampling on straight
+    rays, ``render_baked``'s -- ``importance_u``, ``fused`` and the additional results ``rgb0 / disp0 / acc0``, ``z_std``, ``z_vals`` as there."""
     if rays.device.type != "cuda":
         raise R.Unsupported("rays are not on a ROCm device")
+    if int(N_importance) > 0:
+        if network is not None:
+            raise R.Unsupported("hierarchical sampling of a baked volume behind a network's ray bender (bake the bender: bake_warp, render_baked)")
+        return _render_volume_hierarchical(volume, rays, int(N_samples), int(N_importance), z_vals, importance_u, lindisp, white_bkgd, surface,
+                                           retraw, occupancy, fused)
     lat_t = latents if torch.is_tensor(latents) else None
     if torch.is_grad_enabled() and (rays.requires_grad or (lat_t is not None and lat_t.requires_grad) or volume["raw"].requires_grad
                                     or (z_vals is not None and z_vals.requires_grad)):
@@ -890,6 +897,36 @@ def render_volume(volume, rays, *, network=None, latents=None, N_samples=192, z_
                                         surface=surface)
         return volume_render(volume, rays, N_samples=S, z_vals=z, points4=points4, lindisp=lindisp, white_bkgd=white_bkgd,
                              removal_threshold=removal_threshold, retraw=retraw, surface=surface)
+
+
+def _render_volume_hierarchical(volume, rays, N_samples, I, z_vals, importance_u, lindisp, white_bkgd, surface, retraw, occupancy, fused):
+    """``render_volume(N_importance > 0)``: straight rays, the coarse depths ``render_volume`` takes (``z_vals``, or ``sample_rays``')."""
+    if torch.is_grad_enabled() and (rays.requires_grad or volume["raw"].requires_grad or (z_vals is not None and z_vals.requires_grad)
+                                    or (importance_u is not None and importance_u.requires_grad)):
+        raise R.Unsupported("autograd is enabled (rendering a baked volume has no gradient: render_baked_train has)")
+    dev = rays.device
+    rays = rays.detach().to(dtype=torch.float32).contiguous()
+    S = int(z_vals.shape[1] if z_vals is not None else N_samples)
+    if S < 3:
+        raise ValueError(f"hierarchical sampling needs N_samples >= 3, got {S}")
+    with torch.no_grad():
+        z = z_vals.detach().to(device=dev, dtype=torch.float32).contiguous() if z_vals is not None else sample_rays(rays, S, lindisp)[0]
+        if _use_fused(fused, S, I, not _has_sh(volume) and occupancy is None):
+            return hierarchical_volume_render(volume, None, rays, N_samples=S, N_importance=I, z_vals=z, importance_u=importance_u,
+                                              lindisp=lindisp, white_bkgd=white_bkgd, retraw=retraw, surface=surface)
+
+        def render(N_samples, z_vals, retraw=False, surface=False):
+            points4 = None
+            if surface and not _has_sh(volume):
+                pts = rays[:, None, 0:3] + rays[:, None, 3:6] * z_vals[..., None]   # a product and a sum, each rounded, as the kernels'
+                points4 = torch.cat([pts, torch.zeros_like(pts[..., :1])], -1)
+            kw = dict(N_samples=N_samples, z_vals=z_vals, points4=points4, lindisp=lindisp, white_bkgd=white_bkgd, retraw=retraw, surface=surface)
+            if _has_sh(volume):
+                return sh_volume_render(volume, rays, occupancy=occupancy, **kw)
+            if occupancy is not None:
+                return culled_volume_render(volume, rays, occupancy=occupancy, use_sh=False, **kw)
+            return volume_render(volume, rays, **kw)
+        return _render_hierarchical_composed(render, rays, S, I, z, importance_u, lindisp, white_bkgd, retraw=retraw, surface=surface)
 
 
 def render_volume_frames(volume, render_poses, intrinsics, near, far, *, network=None, latents=None, **kwargs):
@@ -1234,8 +1271,138 @@ def culled_volume_render(volume, rays, *, occupancy, N_samples, use_sh=None, war
     return out
 
 
+# --------------------------------------------------------------------------------------------
+# hierarchical sampling of a baked scene (nrnerf_hierarchical_volume_render): the coarse pass, sample_pdf and the fine
+# pass in one kernel, or composed of the calls above for the records and sizes that have no fused kernel
+# --------------------------------------------------------------------------------------------
+def hierarchical_fused_shape(N_samples, N_importance) -> bool:
+    """Whether the fused kernel takes ``N_samples`` + ``N_importance`` (csrc/nrnerf_hier_volume.h: 3 .. 256 coarse, at most 512 merged)."""
+    S, I = int(N_samples), int(N_importance)
+    return 3 <= S <= _lib.HIER_MAX_COARSE and I >= 1 and S + I <= _lib.HIER_MAX_MERGED
+
+
+def _importance_u(importance_u, N, I, dev):
+    if importance_u is None:
+        return None
+    if tuple(importance_u.shape) != (N, I):
+        raise ValueError(f"importance_u must be {(N, I)}, got {tuple(importance_u.shape)}")
+    return importance_u.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def hierarchical_volume_render(volume, warp, rays, *, N_samples, N_importance, z_vals=None, importance_u=None, lindisp=False, white_bkgd=False,
+                               rigidity_cutoff=None, test_time_scaling=None, removal_threshold=None, coarse=True, retraw=False, weights=False,
+                               alpha=False, surface=False, return_points=False):
+    """``nrnerf_hierarchical_volume_render`` on tensors: ``N_samples`` coarse samples (``z_vals [N, S]`` or the coarse spacing), ``N_importance``
+    more drawn from the coarse weights (``importance_u [N, I]`` or ``linspace(0, 1, I)``), and the fine pass at the merged depths -- one
+    kernel, the bits of ``warped_volume_render`` -> ``nrnerf_composite_forward`` -> ``warped_volume_render``.  ``warp``: a ``bake_warp`` record,
+    or ``None`` for straight rays.  Returns the fine pass' ``rgb_map / disp_map / acc_map``, ``z_std [N]``, ``z_vals [N, S + I]``, the coarse
+    pass' ``rgb0 / disp0 / acc0`` (unless ``coarse=False``) and, as asked for, the fine pass' ``raw``, ``weights``, ``alpha``, ``surface_pts``,
+    ``surface_rigidity``, ``median_index``, ``points4``.  Shapes beyond ``hierarchical_fused_shape`` raise ``NrnerfError`` (UNSUPPORTED):
+    ``render_baked`` composes those.  The value rule: include/nrnerf.h."""
+    vol, lo, hi, g = _grid_parts(volume, "raw", "volume")
+    dev = vol.device
+    a = _lib.HierarchicalVolumeRenderArgs()
+    N, S, keep = _render_front(a, dev, rays, N_samples, z_vals, lindisp, white_bkgd)
+    I = int(N_importance)
+    if I < 1 or S < 3:
+        raise ValueError(f"hierarchical sampling needs N_samples >= 3 and N_importance >= 1, got {S} + {I}")
+    a.n_importance = I
+    u = _importance_u(importance_u, N, I, dev)
+    if u is not None:
+        a.u = u.data_ptr() or None
+    a.volume, a.volume_dtype = vol.data_ptr(), _VOLUME_DTYPES[vol.dtype]
+    a.g[:] = g
+    a.min_point[:], a.max_point[:] = lo.tolist(), hi.tolist()
+    if warp is not None:
+        grid, wlo, whi, wg = _grid_parts(warp, "warp", "warp")
+        if grid.device != dev:
+            raise ValueError(f"the volume is on {dev}, the warp on {grid.device}")
+        a.warp, a.warp_dtype = grid.data_ptr(), _VOLUME_DTYPES[grid.dtype]
+        a.warp_g[:] = wg
+        a.warp_min_point[:], a.warp_max_point[:] = wlo.tolist(), whi.tolist()
+    if rigidity_cutoff is not None:
+        a.has_rigidity_cutoff, a.rigidity_cutoff = 1, float(rigidity_cutoff)
+    if test_time_scaling is not None:
+        a.has_test_time_scaling, a.test_time_scaling = 1, float(test_time_scaling)
+    if removal_threshold is not None:
+        a.has_removal_threshold, a.removal_threshold = 1, float(removal_threshold)
+    out, new = _render_outputs(a, dev, N, S + I, True, weights, alpha, surface)
+    if coarse:
+        a.rgb0, a.disp0, a.acc0 = new("rgb0", N, 3), new("disp0", N), new("acc0", N)
+    a.z_std, a.z_vals = new("z_std", N), new("z_vals", N, S + I)
+    if retraw:
+        a.raw = new("raw", N, S + I, 4)
+    if return_points:
+        a.points4 = new("points4", N, S + I, 4)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().nrnerf_hierarchical_volume_render(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "nrnerf_hierarchical_volume_render")
+    return out
+
+
+def importance_depths(raw, rays, *, N_importance, z_vals=None, importance_u=None, lindisp=False, white_bkgd=False):
+    """``nrnerf_composite_forward`` with ``n_importance > 0`` on the logits ``raw [N, S, 4]`` of a coarse pass, without autograd: ``(z_merged
+    [N, S + I], z_std [N])`` -- the coarse depths (``z_vals`` or the coarse spacing) merged with ``N_importance`` depths drawn from the pass'
+    weights (sample_pdf, run_nerf_helpers.py:651-698; the merge, train.py:910-920)."""
+    dev = raw.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    raw = raw.detach().to(**f32).contiguous()
+    rays = rays.detach().to(**f32).contiguous()
+    N, S, I = int(raw.shape[0]), int(raw.shape[1]), int(N_importance)
+    if I < 1 or S < 3 or S + I > _lib.MAX_SAMPLES:
+        raise ValueError(f"hierarchical sampling needs N_samples >= 3, N_importance >= 1 and at most {_lib.MAX_SAMPLES} samples in all, got {S} + {I}")
+    a = _lib.CompositeArgs()
+    a.struct_size = C.sizeof(_lib.CompositeArgs)
+    a.n_rays, a.n_samples, a.n_importance = N, S, I
+    a.rays, a.ray_stride, a.raw4 = rays.data_ptr() or None, int(rays.shape[1]), raw.data_ptr() or None
+    a.lindisp, a.white_bkgd = int(bool(lindisp)), int(bool(white_bkgd))
+    if z_vals is not None:
+        if tuple(z_vals.shape) != (N, S):
+            raise ValueError(f"z_vals must be {(N, S)}, got {tuple(z_vals.shape)}")
+        z_vals = z_vals.detach().to(**f32).contiguous()
+        a.z = z_vals.data_ptr() or None
+    u = _importance_u(importance_u, N, I, dev)
+    if u is not None:
+        a.u = u.data_ptr() or None
+    maps = torch.empty((N, 5), **f32)            # the pass' rgb, disp, acc: the call requires them, the coarse render has returned them already
+    z_merged, z_std = torch.empty((N, S + I), **f32), torch.empty((N,), **f32)
+    a.rgb, a.disp, a.acc = maps.data_ptr() or None, (maps.data_ptr() + 12 * N) or None, (maps.data_ptr() + 16 * N) or None
+    a.z_std, a.z_merged = z_std.data_ptr() or None, z_merged.data_ptr() or None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().nrnerf_composite_forward(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                   "nrnerf_composite_forward")
+    return z_merged, z_std
+
+
+def _render_hierarchical_composed(render, rays, S, I, z, importance_u, lindisp, white_bkgd, **fine):
+    """The composed route of a hierarchical render, over ANY ``render(N_samples=, z_vals=, retraw=, **outputs)`` of this module that returns
+    ``raw`` under ``retraw``: the render at ``S``, ``importance_depths`` on its logits, the render at ``S + I`` at the merged depths."""
+    if I < 1 or S < 3 or S + I > _lib.MAX_SAMPLES:
+        raise ValueError(f"hierarchical sampling needs N_samples >= 3, N_importance >= 1 and at most {_lib.MAX_SAMPLES} samples in all, got {S} + {I}")
+    first = render(N_samples=S, z_vals=z, retraw=True)
+    z_merged, z_std = importance_depths(first["raw"], rays, N_importance=I, z_vals=z, importance_u=importance_u, lindisp=lindisp,
+                                        white_bkgd=white_bkgd)
+    out = render(N_samples=S + I, z_vals=z_merged, **fine)
+    out.update(rgb0=first["rgb_map"], disp0=first["disp_map"], acc0=first["acc_map"], z_std=z_std, z_vals=z_merged)
+    return out
+
+
+HIER_FUSED_DEFAULT_MERGED = 128     # fused=None takes the fused kernel up to this many merged samples: where it measured faster (DESIGN.md 3.19)
+
+
+def _use_fused(fused, S, I, plain):
+    """``fused=True`` insists on the fused kernel (``Unsupported`` where there is none: an ``"sh"`` record, a mask, a shape it does not take);
+    ``None`` takes it where it is the faster route -- up to 128 merged samples, two per lane: beyond that its coarse pass runs at the fine
+    pass' occupancy and the composed route wins (64 + 128: by 4 %; 64 + 192 and up: 1.4 - 1.8 x) -- and composes otherwise."""
+    can = plain and hierarchical_fused_shape(S, I)
+    if fused and not can:
+        raise R.Unsupported(f"no fused hierarchical kernel for this render ({S} + {I} samples, {'plain' if plain else 'sh / occupancy'} record)")
+    return (can and S + I <= HIER_FUSED_DEFAULT_MERGED) if fused is None else bool(fused)
+
+
 def render_baked(volume, warp, rays, *, N_samples=192, z_vals=None, lindisp=False, white_bkgd=False, rigidity_cutoff=None,
-                 test_time_scaling=None, removal_threshold=None, surface=False, retraw=False, return_points=False, occupancy=None):
+                 test_time_scaling=None, removal_threshold=None, surface=False, retraw=False, return_points=False, occupancy=None,
+                 N_importance=0, importance_u=None, fused=None):
     """A baked scene rendered along ``rays [N, >= 8]`` with no network, no model handle and no latent code: ``volume`` is the canonical ``bake``,
     ``warp`` the ``bake_warp`` of the time step.  ``rgb_map / disp_map / acc_map`` (+ ``raw`` under ``retraw``; ``surface_pts``,
     ``surface_rigidity``, ``median_index`` under ``surface``; ``points4`` under ``return_points``).  The samples are ``N_samples`` of the coarse
@@ -1244,15 +1411,37 @@ def render_baked(volume, warp, rays, *, N_samples=192, z_vals=None, lindisp=Fals
     autograd inputs (``Unsupported``): a preview has no gradient.  A volume record with ``"sh"`` (a view-dependent bake) goes through
     ``sh_volume_render``: the colour of a sample is evaluated at the difference of the ray's consecutive bent points.
     ``occupancy``: the volume's mask (``build_occupancy(volume)``): samples whose bent point falls in an empty block request nothing.  At the
-    mask's ``threshold=0`` every map keeps its bits; ``raw`` is zero at the skipped samples.  ``None`` takes the unmasked kernels."""
+    mask's ``threshold=0`` every map keeps its bits; ``raw`` is zero at the skipped samples.  ``None`` takes the unmasked kernels.
+    ``N_importance > 0``: hierarchical sampling, as the network path does it -- the ``N_samples`` are the coarse pass, ``N_importance`` more are
+    drawn from its weights (``importance_u [N, I]``, or ``linspace(0, 1, I)``) and the maps are the fine pass' over the merged depths; also
+    returned: ``rgb0 / disp0 / acc0`` (the coarse maps), ``z_std [N]`` and ``z_vals [N, S + I]``; ``raw`` and ``points4`` are the fine pass'.
+    ``fused=True`` takes the one-kernel route (``hierarchical_volume_render``), which exists for a record without ``"sh"``, no mask,
+    ``N_samples <= 256`` and ``N_samples + N_importance <= 512`` (``Unsupported`` otherwise); ``False`` composes the calls above (up to 1024
+    samples in all); ``None`` takes the faster of the two: the kernel up to 128 samples in all, the composition beyond.  Both routes return
+    the same bits."""
     if not torch.is_tensor(rays) or rays.device.type != "cuda":
         raise R.Unsupported("rays are not on a ROCm device")
     if torch.is_grad_enabled() and (rays.requires_grad or volume["raw"].requires_grad or warp["warp"].requires_grad
-                                    or (z_vals is not None and z_vals.requires_grad)):
+                                    or (z_vals is not None and z_vals.requires_grad)
+                                    or (importance_u is not None and importance_u.requires_grad)):
         raise R.Unsupported("autograd is enabled (rendering a baked scene has no gradient: render_baked_train has)")
     S = int(z_vals.shape[1] if z_vals is not None else N_samples)
     with torch.no_grad():
         z = None if z_vals is None else z_vals.detach().to(device=rays.device, dtype=torch.float32).contiguous()
+        if int(N_importance) > 0:
+            I = int(N_importance)
+            knobs = dict(lindisp=lindisp, white_bkgd=white_bkgd, rigidity_cutoff=rigidity_cutoff, test_time_scaling=test_time_scaling,
+                         removal_threshold=removal_threshold)
+            if _use_fused(fused, S, I, not _has_sh(volume) and occupancy is None):
+                return hierarchical_volume_render(volume, warp, rays, N_samples=S, N_importance=I, z_vals=z, importance_u=importance_u,
+                                                  retraw=retraw, surface=surface, return_points=return_points, **knobs)
+            one = sh_volume_render if _has_sh(volume) else warped_volume_render
+
+            def render(**kw):
+                return one(volume, rays, warp=warp, occupancy=occupancy, **knobs, **kw) if one is sh_volume_render else \
+                    one(volume, warp, rays, occupancy=occupancy, **knobs, **kw)
+            return _render_hierarchical_composed(render, rays, S, I, z, importance_u, lindisp, white_bkgd, retraw=retraw, surface=surface,
+                                                 return_points=return_points)
         if _has_sh(volume):         # a view-dependent bake: the same kernel with a colour per direction (differences of the bent points)
             return sh_volume_render(volume, rays, warp=warp, N_samples=S, z_vals=z, lindisp=lindisp, white_bkgd=white_bkgd,
                                     rigidity_cutoff=rigidity_cutoff, test_time_scaling=test_time_scaling, removal_threshold=removal_threshold,
@@ -1266,7 +1455,8 @@ def render_baked_frames(volume, warps, render_poses, intrinsics, near, far, **kw
     """``render_baked`` for every camera of ``render_poses`` (``driver.generate_rays`` per frame): ``(rgbs uint8 [F, H, W, 3], disps float32
     [F, H, W])`` on the device, ``rgbs`` by the reference's truncating ``to8b`` (run_nerf_helpers.py:19).  ``warps``: what ``bake_warps``
     returns (``[F, Gz, Gy, Gx, 4]``, one grid per frame; ``[1, ...]`` or what ``bake_warp`` returns: one grid for all frames); ``kwargs``:
-    ``render_baked``'s (``occupancy=`` among them: the mask is the canonical volume's, one serves every frame)."""
+    ``render_baked``'s (``occupancy=`` among them: the mask is the canonical volume's, one serves every frame; ``N_importance=`` and
+    ``importance_u=``: hierarchical sampling, the same uniforms for every frame)."""
     from .driver import generate_rays
     dev = volume["raw"].device
     H, W = int(intrinsics["height"]), int(intrinsics["width"])
