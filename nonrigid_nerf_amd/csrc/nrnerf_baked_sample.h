@@ -1,8 +1,9 @@
-// nrnerf_baked_sample.h -- the device functions of a baked render's sample, shared by the kernels of nrnerf_warp.hip, nrnerf_sh_volume.hip and
-// nrnerf_culled_volume.hip: the bend with its knobs, the removal knob, a sample's bent point in one go, its direction, the spherical-harmonic
-// basis, its place in the volume's grid (Cell) with the requests made there, and the fold of a chunk of coefficients into the colour sums.
-// The text is the one the first two units held; a kernel that includes this gives the bits it gave before.  The value rules: include/nrnerf.h
-// ("baked warps", "view-dependent bakes").
+// nrnerf_baked_sample.h -- the device functions of ONE sample of a baked render: the bend with its knobs, the removal knob, a sample's bent
+// point in one go, its direction, the spherical-harmonic basis, its place in the volume's grid (Cell, with the occupancy mask as a policy:
+// NoMask / BlockMask of nrnerf_volume_lookup.h) with the requests made there, the fold of a chunk of coefficients into the colour sums, and a
+// sample's logits in one go.  The render kernels of nrnerf_warp.hip, nrnerf_sh_volume.hip, nrnerf_culled_volume.hip and nrnerf_hier_volume.hip stand on these; the
+// adjoint of nrnerf_sh_grad.hip takes its cell, direction and basis from here.  The value rules: include/nrnerf.h ("baked warps",
+// "view-dependent bakes", "occupancy masks").
 // No multiply-add is fused that the rule does not name: every product that feeds a sum goes through rounded() (nrnerf_volume_lookup.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,6 +15,10 @@
 namespace nrn {
 
 namespace {
+
+// ---- the samples of a lane whose requests are in flight together in a degree-0 gather (nrnerf_warp.hip has the reasoning): all EPL up to 4,
+// 3 of 6, 2 of 8 and 12, 1 of 16
+constexpr int gather_group(const int EPL) { return EPL <= 4 ? EPL : (EPL == 6 ? 3 : (EPL == 16 ? 1 : 2)); }
 
 // ---- the bent point
 // (u, m) at p -> (bent xyz, m after the cutoff): rnh:563-570
@@ -97,10 +102,13 @@ struct Cell {
     float f[3];
     bool ok;                 // false: the sample is empty
 };
-__device__ __forceinline__ void cell_of(const GridArgs& g, const f32x4 b, Cell& c) {
+// (a sample in an empty block of `mask` is an empty sample: the block's bit is in c.ok before the first request)
+template <class MASK = NoMask>
+__device__ __forceinline__ void cell_of(const GridArgs& g, const f32x4 b, Cell& c, const MASK mask = MASK{}) {
     int i[3];
     grid_cell(g, b[0], b[1], b[2], i, c.f, c.ok);
     c.v = (size_t)i[2] * ((size_t)g.g[0] * (size_t)g.g[1]) + (size_t)i[1] * (size_t)g.g[0] + (size_t)i[0];
+    if constexpr (MASK::on) c.ok = c.ok && mask.bit(i);
 }
 
 // the requests for the eight corners of the four channels 4 j .. 4 j + 3 of an array with 4 * stride channels per vertex (none for an empty
@@ -148,23 +156,26 @@ __device__ __forceinline__ void fold(const float (&Y)[(DEG + 1) * (DEG + 1) - 1]
     pin(col);
 }
 
-// the logits of ONE sample in one go (the lookup kernel): the render kernel's operations in its order
-template <int DEG, bool VHALF>
-__device__ __forceinline__ f32x4 sample_logits(const ShVolumeArgs& a, const f32x4 b, const float (&d)[3]) {
+// the logits of ONE sample in one go (the lookup kernel): the render kernel's operations in its order.  Degree 0: raw after the removal knob,
+// `d` is not read
+template <int DEG, bool VHALF, class MASK = NoMask>
+__device__ __forceinline__ f32x4 sample_logits(const ShVolumeArgs& a, const f32x4 b, const float (&d)[3], const MASK mask = MASK{}) {
     constexpr int CHUNKS = 3 * DEG;
     Cell c;
-    cell_of(a.w.vol, b, c);
+    cell_of(a.w.vol, b, c, mask);
     GridFetch<VHALF> t;
     cell_fetch<VHALF>(a.w.vol.vol, a.w.vol, c, 1, 0, t);
     f32x4 col = grid_value<VHALF>(t);
     col[3] = removed(a.w, col[3], b[3]);
-    pin(col);
-    float Y[(DEG + 1) * (DEG + 1) - 1];
-    sh_basis<DEG>(d, Y);
+    if constexpr (DEG >= 1) {
+        pin(col);
+        float Y[(DEG + 1) * (DEG + 1) - 1];
+        sh_basis<DEG>(d, Y);
 #pragma unroll
-    for (int j = 0; j < CHUNKS; ++j) {
-        cell_fetch<VHALF>(a.sh, a.w.vol, c, CHUNKS, j, t);
-        fold<DEG>(Y, grid_value<VHALF>(t), j, col);
+        for (int j = 0; j < CHUNKS; ++j) {
+            cell_fetch<VHALF>(a.sh, a.w.vol, c, CHUNKS, j, t);
+            fold<DEG>(Y, grid_value<VHALF>(t), j, col);
+        }
     }
     return col;
 }

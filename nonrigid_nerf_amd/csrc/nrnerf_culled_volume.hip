@@ -11,6 +11,8 @@
 // warp): chosen at run time inside one kernel, the allocator keeps the warp's and the volume's corners of a group apart and the EPL = 4 kernel
 // needs 358 registers instead of 217.
 // culled_sh_render_kernel<DEG, EPL, VHALF, WHALF> (degree 1 / 2): sh_render_kernel's text with the masked cell.
+// The mask is a policy of the shared lookup (BlockMask: grid_fetch, nrnerf_volume_lookup.h; cell_of and sample_logits, nrnerf_baked_sample.h).
+// The ray loops are texts of their own next to the unmasked kernels': shared behind a function they measured slower.
 // culled_lookup_kernel<DEG, VHALF, WHALF>: the same device functions, one thread per sample, no compositing: the render kernels' raw / points4
 // bits.
 // The mask is read through global memory: a 256^3 volume at the default block is 4 KiB of words, which every wave of a CU keeps hitting in the
@@ -20,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "nrnerf_culled_volume.h"
+#include "nrnerf_baked_launch.h"
 #include "nrnerf_baked_sample.h"
 
 #ifndef NRN_CULL_DEGREE
@@ -30,69 +33,7 @@ namespace nrn {
 
 namespace {
 
-constexpr int CULL_WAVES = 4;           // waves (= rays in flight) per workgroup
-constexpr int CULL_MAXS = 1024;         // NRNERF_MAX_SAMPLES: EPL <= 16
-
-// the bit of the block of cell i: the block is i >> k per axis (grid_cell clamps i to 0 .. g - 2, so the block exists whether the sample is
-// inside the box or not)
-__device__ __forceinline__ bool block_bit(const CulledVolumeArgs& a, const int (&i)[3]) {
-    const int blk = ((i[2] >> a.k) * a.nb[1] + (i[1] >> a.k)) * a.nb[0] + (i[0] >> a.k);
-    const unsigned word = ((const __attribute__((address_space(1))) unsigned*)a.occ)[blk >> 5];
-    return ((word >> (blk & 31)) & 1u) != 0u;
-}
-
-// cell_of (nrnerf_baked_sample.h) with the mask: the block's bit joins the sample's flag
-__device__ __forceinline__ void culled_cell_of(const CulledVolumeArgs& a, const f32x4 b, Cell& c) {
-    const GridArgs& g = a.s.w.vol;
-    int i[3];
-    grid_cell(g, b[0], b[1], b[2], i, c.f, c.ok);
-    c.v = (size_t)i[2] * ((size_t)g.g[0] * (size_t)g.g[1]) + (size_t)i[1] * (size_t)g.g[0] + (size_t)i[0];
-    c.ok = c.ok && block_bit(a, i);
-}
-
-// grid_fetch (nrnerf_volume_lookup.h) of the volume with the mask: the block's bit joins the flag before the corners are requested
-template <bool HALF>
-__device__ __forceinline__ void culled_grid_fetch(const CulledVolumeArgs& a, const float px, const float py, const float pz, GridFetch<HALF>& t) {
-    typedef typename GridFetch<HALF>::vertex vertex;
-    const GridArgs& g = a.s.w.vol;
-    int i[3];
-    grid_cell(g, px, py, pz, i, t.f, t.ok);
-    t.ok = t.ok && block_bit(a, i);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) t.c[k] = vertex{};
-    if (t.ok) {
-        const size_t gx = (size_t)g.g[0], gxy = gx * (size_t)g.g[1];
-        const size_t v = (size_t)i[2] * gxy + (size_t)i[1] * gx + (size_t)i[0];
-        const __attribute__((address_space(1))) vertex* q = (const __attribute__((address_space(1))) vertex*)g.vol;
-        t.c[0] = q[v];             t.c[1] = q[v + 1];
-        t.c[2] = q[v + gx];        t.c[3] = q[v + gx + 1];
-        t.c[4] = q[v + gxy];       t.c[5] = q[v + gxy + 1];
-        t.c[6] = q[v + gxy + gx];  t.c[7] = q[v + gxy + gx + 1];
-    }
-}
-
-// sample_logits (nrnerf_baked_sample.h) with the masked cell; degree 0: raw after the removal knob, `d` is not read
-template <int DEG, bool VHALF>
-__device__ __forceinline__ f32x4 culled_sample_logits(const CulledVolumeArgs& a, const f32x4 b, const float (&d)[3]) {
-    constexpr int CHUNKS = 3 * DEG;
-    Cell c;
-    culled_cell_of(a, b, c);
-    GridFetch<VHALF> t;
-    cell_fetch<VHALF>(a.s.w.vol.vol, a.s.w.vol, c, 1, 0, t);
-    f32x4 col = grid_value<VHALF>(t);
-    col[3] = removed(a.s.w, col[3], b[3]);
-    if constexpr (DEG >= 1) {
-        pin(col);
-        float Y[(DEG + 1) * (DEG + 1) - 1];
-        sh_basis<DEG>(d, Y);
-#pragma unroll
-        for (int j = 0; j < CHUNKS; ++j) {
-            cell_fetch<VHALF>(a.s.sh, a.s.w.vol, c, CHUNKS, j, t);
-            fold<DEG>(Y, grid_value<VHALF>(t), j, col);
-        }
-    }
-    return col;
-}
+__device__ __forceinline__ BlockMask block_mask(const CulledVolumeArgs& a) { return BlockMask{a.occ, a.k, {a.nb[0], a.nb[1]}}; }
 
 // the surface outputs, as the parents have them: the sample surface_index picks on the weights composite_ray returned, bent again
 template <int EPL, bool WHALF>
@@ -111,15 +52,15 @@ __device__ __forceinline__ void surface_outputs(const ShVolumeArgs& a, const int
 constexpr int SRC_STRAIGHT = 0, SRC_POINTS4 = 1, SRC_WARP = 2;
 
 template <int EPL, bool VHALF, int SRC, bool WHALF>
-__global__ void __launch_bounds__(CULL_WAVES * 64) culled_render_kernel(const CulledVolumeArgs a) {
+__global__ void __launch_bounds__(BAKED_WAVES * 64) culled_render_kernel(const CulledVolumeArgs a) {
     constexpr bool WARPED = SRC == SRC_WARP;
-    constexpr int GROUP = EPL <= 4 ? EPL : (EPL == 6 ? 3 : (EPL == 16 ? 1 : 2));
+    constexpr int GROUP = gather_group(EPL);
     static_assert(EPL % GROUP == 0, "whole groups");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const WarpArgs& w = a.s.w;
     const int S = w.c.S;
-    const long long step = (long long)gridDim.x * CULL_WAVES;
-    for (long long rr = (long long)blockIdx.x * CULL_WAVES + wave; rr < w.c.n_rays; rr += step) {
+    const long long step = (long long)gridDim.x * BAKED_WAVES;
+    for (long long rr = (long long)blockIdx.x * BAKED_WAVES + wave; rr < w.c.n_rays; rr += step) {
         const int ray = (int)rr;
         const __attribute__((address_space(1))) float* rp = gmem(w.c.rays) + (size_t)ray * w.c.ray_stride;
         f32x4 raw[EPL];
@@ -143,7 +84,7 @@ __global__ void __launch_bounds__(CULL_WAVES * 64) culled_render_kernel(const Cu
             for (int k = 0; k < GROUP; ++k) {
                 if constexpr (WARPED) b[k] = bend(w, p[k], grid_value<WHALF>(tw[k]));
                 else { b[k][0] = p[k][0]; b[k][1] = p[k][1]; b[k][2] = p[k][2]; b[k][3] = m[k]; }
-                culled_grid_fetch<VHALF>(a, b[k][0], b[k][1], b[k][2], tv[k]);
+                grid_fetch<VHALF>(w.vol, b[k][0], b[k][1], b[k][2], tv[k], block_mask(a));
             }
 #pragma unroll
             for (int k = 0; k < GROUP; ++k) {
@@ -164,18 +105,18 @@ __global__ void __launch_bounds__(CULL_WAVES * 64) culled_render_kernel(const Cu
 }
 
 template <int DEG, int EPL, bool VHALF, bool WHALF>
-__global__ void __launch_bounds__(CULL_WAVES * 64, 2) culled_sh_render_kernel(const CulledVolumeArgs a) {
+__global__ void __launch_bounds__(BAKED_WAVES * 64, 2) culled_sh_render_kernel(const CulledVolumeArgs a) {
     constexpr bool PIPE = EPL <= 4;             // two chunks of `sh` in flight (64 registers of corners in float32), else one
     constexpr bool PARK = EPL == 16;            // the samples' logits wait for composite_ray in LDS (a lane reads what it wrote: no barrier), else in registers
     constexpr bool EARLY = EPL <= 8;            // chunk 0 is requested together with raw's corners, else after raw is interpolated
     constexpr int CHUNKS = 3 * DEG;
-    __shared__ f32x4 parked[PARK ? CULL_WAVES * 64 * EPL : 1];
+    __shared__ f32x4 parked[PARK ? BAKED_WAVES * 64 * EPL : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const ShVolumeArgs& s = a.s;
     const int S = s.w.c.S;
     const bool warped = s.w.warp.vol != nullptr;
-    const long long step = (long long)gridDim.x * CULL_WAVES;
-    for (long long rr = (long long)blockIdx.x * CULL_WAVES + wave; rr < s.w.c.n_rays; rr += step) {
+    const long long step = (long long)gridDim.x * BAKED_WAVES;
+    for (long long rr = (long long)blockIdx.x * BAKED_WAVES + wave; rr < s.w.c.n_rays; rr += step) {
         const int ray = (int)rr;
         const __attribute__((address_space(1))) float* rp = gmem(s.w.c.rays) + (size_t)ray * s.w.c.ray_stride;
         f32x4 raw[PARK ? 1 : EPL];
@@ -203,7 +144,7 @@ __global__ void __launch_bounds__(CULL_WAVES * 64, 2) culled_sh_render_kernel(co
             }
             Cell cell;
             GridFetch<VHALF> tv, tu;
-            culled_cell_of(a, b, cell);             // the block's bit is in cell.ok before the first request
+            cell_of(s.w.vol, b, cell, block_mask(a));            // the block's bit is in cell.ok before the first request
             cell_fetch<VHALF>(s.w.vol.vol, s.w.vol, cell, 1, 0, tv);
             if (EARLY) cell_fetch<VHALF>(s.sh, s.w.vol, cell, CHUNKS, 0, tu);
             if (!s.ray_dirs) {
@@ -258,23 +199,16 @@ __global__ void __launch_bounds__(256) culled_lookup_kernel(const CulledVolumeAr
                 else if (i == 0) diff_dir(sample_bent<WHALF>(s, ray, 1), b, d);      // d_0 = d_1
                 else diff_dir(b, sample_bent<WHALF>(s, ray, i - 1), d);
             }
-            *(__attribute__((address_space(1))) f32x4*)(gmem(s.w.raw_out) + (size_t)t * 4) = culled_sample_logits<DEG, VHALF>(a, b, d);
+            *(__attribute__((address_space(1))) f32x4*)(gmem(s.w.raw_out) + (size_t)t * 4) = sample_logits<DEG, VHALF>(s, b, d, block_mask(a));
         }
     }
 }
 
-template <class KERNEL>
-hipError_t launch(KERNEL kernel, const CulledVolumeArgs& a, const dim3 grid, const dim3 block, hipStream_t stream) {
-    hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
-    return hipGetLastError();
-}
-
 template <int DEG, int EPL>
 hipError_t launch_epl(const CulledVolumeArgs& a, int num_cus, hipStream_t stream) {
-    const long long want = ((long long)a.s.w.c.n_rays + CULL_WAVES - 1) / CULL_WAVES, cap = (long long)(num_cus > 0 ? num_cus : 256) * 16;
-    const dim3 grid((unsigned)(want < cap ? want : cap)), block(CULL_WAVES * 64);
-    const int storage = (a.s.w.vol.half ? 2 : 0) | (a.s.w.warp.half ? 1 : 0);
+    const dim3 grid = ray_loop_grid(a.s.w.c.n_rays, num_cus), block(BAKED_WAVES * 64);
     if constexpr (DEG == 0) {
+        // without a warp its storage is no parameter
         if (a.s.points4_in) {
             if (a.s.w.vol.half) return launch(culled_render_kernel<EPL, true, SRC_POINTS4, false>, a, grid, block, stream);
             return launch(culled_render_kernel<EPL, false, SRC_POINTS4, false>, a, grid, block, stream);
@@ -283,19 +217,13 @@ hipError_t launch_epl(const CulledVolumeArgs& a, int num_cus, hipStream_t stream
             if (a.s.w.vol.half) return launch(culled_render_kernel<EPL, true, SRC_STRAIGHT, false>, a, grid, block, stream);
             return launch(culled_render_kernel<EPL, false, SRC_STRAIGHT, false>, a, grid, block, stream);
         }
-        switch (storage) {
-            case 0: return launch(culled_render_kernel<EPL, false, SRC_WARP, false>, a, grid, block, stream);
-            case 1: return launch(culled_render_kernel<EPL, false, SRC_WARP, true>, a, grid, block, stream);
-            case 2: return launch(culled_render_kernel<EPL, true, SRC_WARP, false>, a, grid, block, stream);
-            default: return launch(culled_render_kernel<EPL, true, SRC_WARP, true>, a, grid, block, stream);
-        }
+        return with_storage(a.s.w.vol.half, a.s.w.warp.half, [&](auto vh, auto wh) {
+            return launch(culled_render_kernel<EPL, vh(), SRC_WARP, wh()>, a, grid, block, stream);
+        });
     } else {
-        switch (storage) {
-            case 0: return launch(culled_sh_render_kernel<DEG, EPL, false, false>, a, grid, block, stream);
-            case 1: return launch(culled_sh_render_kernel<DEG, EPL, false, true>, a, grid, block, stream);
-            case 2: return launch(culled_sh_render_kernel<DEG, EPL, true, false>, a, grid, block, stream);
-            default: return launch(culled_sh_render_kernel<DEG, EPL, true, true>, a, grid, block, stream);
-        }
+        return with_storage(a.s.w.vol.half, a.s.w.warp.half, [&](auto vh, auto wh) {
+            return launch(culled_sh_render_kernel<DEG, EPL, vh(), wh()>, a, grid, block, stream);
+        });
     }
 }
 
@@ -305,7 +233,7 @@ template <>
 hipError_t launch_culled_volume_render_degree<NRN_CULL_DEGREE>(const CulledVolumeArgs& a, int num_cus, hipStream_t stream) {
     constexpr int DEG = NRN_CULL_DEGREE;
     const WarpArgs& w = a.s.w;
-    if (w.c.S < 1 || w.c.S > CULL_MAXS || a.s.degree != DEG || (DEG >= 1 && !a.s.ray_dirs && w.c.S < 2)) return hipErrorInvalidValue;
+    if (w.c.S < 1 || w.c.S > BAKED_MAXS || a.s.degree != DEG || (DEG >= 1 && !a.s.ray_dirs && w.c.S < 2)) return hipErrorInvalidValue;
     if (w.warp.vol && a.s.points4_in) return hipErrorInvalidValue;
     // (noise and the range of k are launch_culled_volume_render's checks, the one caller: nrnerf_culled_volume.h)
     if (!a.occ) return hipErrorInvalidValue;
@@ -313,14 +241,9 @@ hipError_t launch_culled_volume_render_degree<NRN_CULL_DEGREE>(const CulledVolum
     if (w.c.n_rays <= 0) return hipSuccess;
     if (!w.c.rgb) {                         // the lookup alone
         if (!w.raw_out && !w.points4_out) return hipErrorInvalidValue;
-        const long long want = ((long long)w.c.n_rays * w.c.S + 255) / 256, cap = (long long)(num_cus > 0 ? num_cus : 256) * 32;
-        const dim3 grid((unsigned)(want < cap ? want : cap)), block(256);
-        switch ((w.vol.half ? 2 : 0) | (w.warp.half ? 1 : 0)) {
-            case 0: return launch(culled_lookup_kernel<DEG, false, false>, a, grid, block, stream);
-            case 1: return launch(culled_lookup_kernel<DEG, false, true>, a, grid, block, stream);
-            case 2: return launch(culled_lookup_kernel<DEG, true, false>, a, grid, block, stream);
-            default: return launch(culled_lookup_kernel<DEG, true, true>, a, grid, block, stream);
-        }
+        return with_storage(w.vol.half, w.warp.half, [&](auto vh, auto wh) {
+            return launch(culled_lookup_kernel<DEG, vh(), wh()>, a, sample_grid(w.c.n_rays, w.c.S, num_cus), dim3(256), stream);
+        });
     }
     return with_epl(w.c.S, [&](auto epl) { return launch_epl<DEG, epl()>(a, num_cus, stream); });
 }

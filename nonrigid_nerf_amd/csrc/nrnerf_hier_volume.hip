@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "nrnerf_hier_volume.h"
+#include "nrnerf_baked_launch.h"
 #include "nrnerf_composite_ray.h"
 #include "nrnerf_volume_lookup.h"
 #include "nrnerf_baked_sample.h"
@@ -28,14 +29,12 @@ namespace nrn {
 
 namespace {
 
-constexpr int HIER_WAVES = 4;           // waves (= rays in flight) per workgroup
-
 // the sample loop of warped_render_kernel for the S samples of one pass: sample i lies at depth_at(i); raw[k] = the logits of sample
 // lane * EPL + k (beyond S: the last sample's, as composite_ray asks for).  No warp: an empty request, (u, m) = 0
 template <int EPL, bool VHALF, bool WHALF, class DEPTH>
 __device__ __forceinline__ void gather_ray(const WarpArgs& a, const __attribute__((address_space(1))) float* rp, const int ray, const int lane,
                                            const int S, DEPTH&& depth_at, f32x4 (&raw)[EPL], float* raw_out, float* points4_out) {
-    constexpr int GROUP = EPL <= 4 ? EPL : (EPL == 6 ? 3 : 2);
+    constexpr int GROUP = gather_group(EPL);
     static_assert(EPL % GROUP == 0, "whole groups");
     const bool has_warp = a.warp.vol != nullptr;
 #pragma unroll
@@ -74,19 +73,19 @@ __device__ __forceinline__ void gather_ray(const WarpArgs& a, const __attribute_
 }
 
 template <int EPL_C, int EPL_F, bool VHALF, bool WHALF>
-__global__ void __launch_bounds__(HIER_WAVES * 64) hier_render_kernel(const HierArgs a) {
+__global__ void __launch_bounds__(BAKED_WAVES * 64) hier_render_kernel(const HierArgs a) {
     static_assert(EPL_F >= EPL_C, "the merged depths hold the coarse ones");
     constexpr int NC = 64 * EPL_C, NF = 64 * EPL_F;
     constexpr int NM = 2 * NC > NF ? 2 * NC : NF;            // the merged depths lie over s_cdf and s_bins
-    __shared__ float lds[HIER_WAVES][NF + NM];
+    __shared__ float lds[BAKED_WAVES][NF + NM];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float* const s_z = lds[wave];
     float* const s_cdf = s_z + NF;
     float* const s_bins = s_cdf + NC;
     float* const s_m = s_cdf;
     const int Sc = a.cc.S, Sf = a.w.c.S;
-    const long long step = (long long)gridDim.x * HIER_WAVES;
-    for (long long rr = (long long)blockIdx.x * HIER_WAVES + wave; rr < a.cc.n_rays; rr += step) {
+    const long long step = (long long)gridDim.x * BAKED_WAVES;
+    for (long long rr = (long long)blockIdx.x * BAKED_WAVES + wave; rr < a.cc.n_rays; rr += step) {
         const int ray = (int)rr;
         const __attribute__((address_space(1))) float* rp = gmem(a.cc.rays) + (size_t)ray * a.cc.ray_stride;
         // ---- the coarse pass: its maps (when asked for), its depths and weights for the sampling
@@ -132,25 +131,14 @@ __global__ void __launch_bounds__(HIER_WAVES * 64) hier_render_kernel(const Hier
     }
 }
 
-template <class KERNEL>
-hipError_t launch(KERNEL kernel, const HierArgs& a, const dim3 grid, const dim3 block, hipStream_t stream) {
-    hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
-    return hipGetLastError();
-}
-
 template <int EPL_C, int EPL_F>
 hipError_t launch_epl(const HierArgs& a, int num_cus, hipStream_t stream) {
     if constexpr (EPL_F < EPL_C || EPL_F > 8) {
         return hipErrorInvalidValue;
     } else {
-        const long long want = ((long long)a.cc.n_rays + HIER_WAVES - 1) / HIER_WAVES, cap = (long long)(num_cus > 0 ? num_cus : 256) * 16;
-        const dim3 grid((unsigned)(want < cap ? want : cap)), block(HIER_WAVES * 64);
-        switch ((a.w.vol.half ? 2 : 0) | (a.w.warp.half ? 1 : 0)) {
-            case 0: return launch(hier_render_kernel<EPL_C, EPL_F, false, false>, a, grid, block, stream);
-            case 1: return launch(hier_render_kernel<EPL_C, EPL_F, false, true>, a, grid, block, stream);
-            case 2: return launch(hier_render_kernel<EPL_C, EPL_F, true, false>, a, grid, block, stream);
-            default: return launch(hier_render_kernel<EPL_C, EPL_F, true, true>, a, grid, block, stream);
-        }
+        return with_storage(a.w.vol.half, a.w.warp.half, [&](auto vh, auto wh) {
+            return launch(hier_render_kernel<EPL_C, EPL_F, vh(), wh()>, a, ray_loop_grid(a.cc.n_rays, num_cus), dim3(BAKED_WAVES * 64), stream);
+        });
     }
 }
 

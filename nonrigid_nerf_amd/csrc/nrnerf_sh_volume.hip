@@ -18,11 +18,13 @@
 // One translation unit per degree (NRN_SH_DEGREE), so that the two build side by side.
 // The device functions of a sample (bend, removed, sample_bent, unit_dir, sh_basis, Cell, cell_of, cell_fetch, pin, fold, sample_logits) live
 // in nrnerf_baked_sample.h, shared with nrnerf_warp.hip and nrnerf_culled_volume.hip.
-// A COPY of sh_render_kernel / sh_lookup_kernel with an occupancy bit in the sample's flag is culled_sh_render_kernel / culled_lookup_kernel
-// (nrnerf_culled_volume.hip; these objects must keep exactly their kernels): a fix here belongs there too.
+// culled_sh_render_kernel / culled_lookup_kernel (nrnerf_culled_volume.hip) are sh_render_kernel's / sh_lookup_kernel's text with the occupancy
+// mask in cell_of: two texts, because shared behind a function they measured slower.  The launch idiom:
+// nrnerf_baked_launch.h.
 #include <hip/hip_runtime.h>
 
 #include "nrnerf_sh_volume.h"
+#include "nrnerf_baked_launch.h"
 #include "nrnerf_composite_ray.h"
 #include "nrnerf_volume_lookup.h"
 #include "nrnerf_baked_sample.h"
@@ -35,21 +37,18 @@ namespace nrn {
 
 namespace {
 
-constexpr int SH_WAVES = 4;             // waves (= rays in flight) per workgroup
-constexpr int SH_MAXS = 1024;           // NRNERF_MAX_SAMPLES: EPL <= 16
-
 template <int DEG, int EPL, bool VHALF, bool WHALF>
-__global__ void __launch_bounds__(SH_WAVES * 64, 2) sh_render_kernel(const ShVolumeArgs a) {
+__global__ void __launch_bounds__(BAKED_WAVES * 64, 2) sh_render_kernel(const ShVolumeArgs a) {
     constexpr bool PIPE = EPL <= 4;             // two chunks of `sh` in flight (64 registers of corners in float32), else one
     constexpr bool PARK = EPL == 16;            // the samples' logits wait for composite_ray in LDS (a lane reads what it wrote: no barrier), else in registers
     constexpr bool EARLY = EPL <= 8;            // chunk 0 is requested together with raw's corners, else after raw is interpolated
     constexpr int CHUNKS = 3 * DEG;
-    __shared__ f32x4 parked[PARK ? SH_WAVES * 64 * EPL : 1];
+    __shared__ f32x4 parked[PARK ? BAKED_WAVES * 64 * EPL : 1];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int S = a.w.c.S;
     const bool warped = a.w.warp.vol != nullptr;
-    const long long step = (long long)gridDim.x * SH_WAVES;
-    for (long long rr = (long long)blockIdx.x * SH_WAVES + wave; rr < a.w.c.n_rays; rr += step) {
+    const long long step = (long long)gridDim.x * BAKED_WAVES;
+    for (long long rr = (long long)blockIdx.x * BAKED_WAVES + wave; rr < a.w.c.n_rays; rr += step) {
         const int ray = (int)rr;
         const __attribute__((address_space(1))) float* rp = gmem(a.w.c.rays) + (size_t)ray * a.w.c.ray_stride;
         f32x4 raw[PARK ? 1 : EPL];
@@ -145,44 +144,25 @@ __global__ void __launch_bounds__(256) sh_lookup_kernel(const ShVolumeArgs a) {
     }
 }
 
-template <class KERNEL>
-hipError_t launch(KERNEL kernel, const ShVolumeArgs& a, const dim3 grid, const dim3 block, hipStream_t stream) {
-    hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
-    return hipGetLastError();
-}
-
-template <int DEG, int EPL>
-hipError_t launch_epl(const ShVolumeArgs& a, int num_cus, hipStream_t stream) {
-    const long long want = ((long long)a.w.c.n_rays + SH_WAVES - 1) / SH_WAVES, cap = (long long)(num_cus > 0 ? num_cus : 256) * 16;
-    const dim3 grid((unsigned)(want < cap ? want : cap)), block(SH_WAVES * 64);
-    switch ((a.w.vol.half ? 2 : 0) | (a.w.warp.half ? 1 : 0)) {
-        case 0: return launch(sh_render_kernel<DEG, EPL, false, false>, a, grid, block, stream);
-        case 1: return launch(sh_render_kernel<DEG, EPL, false, true>, a, grid, block, stream);
-        case 2: return launch(sh_render_kernel<DEG, EPL, true, false>, a, grid, block, stream);
-        default: return launch(sh_render_kernel<DEG, EPL, true, true>, a, grid, block, stream);
-    }
-}
-
 }  // namespace
 
 template <>
 hipError_t launch_sh_volume_render_degree<NRN_SH_DEGREE>(const ShVolumeArgs& a, int num_cus, hipStream_t stream) {
     constexpr int DEG = NRN_SH_DEGREE;
-    if (a.w.c.S < 1 || a.w.c.S > SH_MAXS || a.degree != DEG || (!a.ray_dirs && a.w.c.S < 2)) return hipErrorInvalidValue;
+    if (a.w.c.S < 1 || a.w.c.S > BAKED_MAXS || a.degree != DEG || (!a.ray_dirs && a.w.c.S < 2)) return hipErrorInvalidValue;
     if (a.w.warp.vol && a.points4_in) return hipErrorInvalidValue;
     if (a.w.c.n_rays <= 0) return hipSuccess;
     if (!a.w.c.rgb) {                       // the lookup alone
         if (!a.w.raw_out && !a.w.points4_out) return hipErrorInvalidValue;
-        const long long want = ((long long)a.w.c.n_rays * a.w.c.S + 255) / 256, cap = (long long)(num_cus > 0 ? num_cus : 256) * 32;
-        const dim3 grid((unsigned)(want < cap ? want : cap)), block(256);
-        switch ((a.w.vol.half ? 2 : 0) | (a.w.warp.half ? 1 : 0)) {
-            case 0: return launch(sh_lookup_kernel<DEG, false, false>, a, grid, block, stream);
-            case 1: return launch(sh_lookup_kernel<DEG, false, true>, a, grid, block, stream);
-            case 2: return launch(sh_lookup_kernel<DEG, true, false>, a, grid, block, stream);
-            default: return launch(sh_lookup_kernel<DEG, true, true>, a, grid, block, stream);
-        }
+        return with_storage(a.w.vol.half, a.w.warp.half, [&](auto vh, auto wh) {
+            return launch(sh_lookup_kernel<DEG, vh(), wh()>, a, sample_grid(a.w.c.n_rays, a.w.c.S, num_cus), dim3(256), stream);
+        });
     }
-    return with_epl(a.w.c.S, [&](auto epl) { return launch_epl<DEG, epl()>(a, num_cus, stream); });
+    return with_epl(a.w.c.S, [&](auto epl) {
+        return with_storage(a.w.vol.half, a.w.warp.half, [&](auto vh, auto wh) {
+            return launch(sh_render_kernel<DEG, epl(), vh(), wh()>, a, ray_loop_grid(a.w.c.n_rays, num_cus), dim3(BAKED_WAVES * 64), stream);
+        });
+    });
 }
 
 }  // namespace nrn

@@ -7,21 +7,20 @@
 // 16 * EPL contiguous bytes, coalesced across the wave.  Each lane gathers its samples' logits ONCE into registers (eight corners per sample:
 // four pairs of x-neighbours, a pair adjacent in memory and requested together), then composite_ray<EPL> runs on those registers.
 // volume_lookup_kernel<HALF>: the same per-sample device function, one thread per sample, the logits alone (no compositing).
-// The lookup itself (lerp4 / load_pair / volume_at) lives in nrnerf_volume_lookup.h, shared with nrnerf_warp.hip.
+// The lookup itself (lerp4 / load_pair / volume_at) lives in nrnerf_volume_lookup.h, shared with the other baked render kernels; the launch
+// idiom is theirs too (nrnerf_baked_launch.h).
 // Every multiply-add is spelled __fmaf_rn and every product that feeds a sum or a difference goes through rounded(): this build's
 // -ffp-contract=fast would otherwise fuse them per instantiation (nrnerf_composite_ray.h), and the two kernels must give the same bits.
 #include <hip/hip_runtime.h>
 
 #include "nrnerf_volume.h"
+#include "nrnerf_baked_launch.h"
 #include "nrnerf_composite_ray.h"
 #include "nrnerf_volume_lookup.h"
 
 namespace nrn {
 
 namespace {
-
-constexpr int VOL_WAVES = 4;            // waves (= rays in flight) per workgroup
-constexpr int VOL_MAXS = 1024;          // NRNERF_MAX_SAMPLES: EPL <= 16
 
 // the logits of sample ic (< S) of `ray`: its point (points4, or sample_point at sample_depth),
 // the lookup, the removal knob
@@ -42,11 +41,11 @@ __device__ __forceinline__ f32x4 sample_logits(const VolumeArgs& a, const int ra
 }
 
 template <int EPL, bool HALF>
-__global__ void __launch_bounds__(VOL_WAVES * 64) volume_render_kernel(const VolumeArgs a) {
+__global__ void __launch_bounds__(BAKED_WAVES * 64) volume_render_kernel(const VolumeArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int S = a.c.S;
-    const long long step = (long long)gridDim.x * VOL_WAVES;
-    for (long long rr = (long long)blockIdx.x * VOL_WAVES + wave; rr < a.c.n_rays; rr += step) {
+    const long long step = (long long)gridDim.x * BAKED_WAVES;
+    for (long long rr = (long long)blockIdx.x * BAKED_WAVES + wave; rr < a.c.n_rays; rr += step) {
         const int ray = (int)rr;
         f32x4 raw[EPL];
 #pragma unroll
@@ -73,29 +72,22 @@ __global__ void __launch_bounds__(256) volume_lookup_kernel(const VolumeArgs a) 
     }
 }
 
-template <int EPL>
-hipError_t launch_epl(const VolumeArgs& a, int num_cus, hipStream_t stream) {
-    const long long want = ((long long)a.c.n_rays + VOL_WAVES - 1) / VOL_WAVES, cap = (long long)(num_cus > 0 ? num_cus : 256) * 16;
-    const dim3 grid((unsigned)(want < cap ? want : cap));
-    if (a.grid.half) hipLaunchKernelGGL((volume_render_kernel<EPL, true>), grid, dim3(VOL_WAVES * 64), 0, stream, a);
-    else hipLaunchKernelGGL((volume_render_kernel<EPL, false>), grid, dim3(VOL_WAVES * 64), 0, stream, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_volume_render(const VolumeArgs& a, int num_cus, hipStream_t stream) {
-    if (a.c.S < 1 || a.c.S > VOL_MAXS) return hipErrorInvalidValue;
+    if (a.c.S < 1 || a.c.S > BAKED_MAXS) return hipErrorInvalidValue;
     if (a.c.n_rays <= 0) return hipSuccess;
     if (!a.c.rgb) {                         // the lookup alone
         if (!a.raw_out) return hipErrorInvalidValue;
-        const long long want = ((long long)a.c.n_rays * a.c.S + 255) / 256, cap = (long long)(num_cus > 0 ? num_cus : 256) * 32;
-        const dim3 grid((unsigned)(want < cap ? want : cap));
-        if (a.grid.half) hipLaunchKernelGGL(volume_lookup_kernel<true>, grid, dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL(volume_lookup_kernel<false>, grid, dim3(256), 0, stream, a);
-        return hipGetLastError();
+        const dim3 grid = sample_grid(a.c.n_rays, a.c.S, num_cus);
+        if (a.grid.half) return launch(volume_lookup_kernel<true>, a, grid, dim3(256), stream);
+        return launch(volume_lookup_kernel<false>, a, grid, dim3(256), stream);
     }
-    return with_epl(a.c.S, [&](auto epl) { return launch_epl<epl()>(a, num_cus, stream); });
+    return with_epl(a.c.S, [&](auto epl) {
+        const dim3 grid = ray_loop_grid(a.c.n_rays, num_cus), block(BAKED_WAVES * 64);
+        if (a.grid.half) return launch(volume_render_kernel<epl(), true>, a, grid, block, stream);
+        return launch(volume_render_kernel<epl(), false>, a, grid, block, stream);
+    });
 }
 
 }  // namespace nrn

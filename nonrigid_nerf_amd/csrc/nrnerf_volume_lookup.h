@@ -1,6 +1,7 @@
 // nrnerf_volume_lookup.h -- the value of a vertex-centred grid of four channels at a point (include/nrnerf.h, "THE VALUE AT A POINT"): device
 // functions shared by nrnerf_volume.hip (the canonical volume at ready-made points) and nrnerf_warp.hip (an offset grid, then the canonical
 // volume at the bent point).  A grid is a GridArgs (nrnerf_volume.h); where a point falls in it is grid_cell, used by both forms of the lookup.
+// The occupancy mask of a baked render is a policy of the two-step form (NoMask / BlockMask): there is one grid_fetch.
 // Every multiply-add is spelled __fmaf_rn and every product that feeds a sum or a difference goes through rounded(): this build's
 // -ffp-contract=fast would otherwise fuse them per instantiation (nrnerf_composite_ray.h), and every kernel that includes this must give the
 // same bits.
@@ -92,13 +93,33 @@ struct GridFetch {
     bool ok;                 // false: the sample is empty, nothing was loaded
 };
 
-// where the point falls, and the requests for its eight corners (none for an empty sample)
-// (culled_grid_fetch of nrnerf_culled_volume.hip is this text with an occupancy bit in t.ok: a fix here belongs there too)
-template <bool HALF>
-__device__ __forceinline__ void grid_fetch(const GridArgs& a, const float px, const float py, const float pz, GridFetch<HALF>& t) {
+// ---- the occupancy mask as a policy of the lookup: NoMask compiles away; BlockMask ANDs the bit of the cell's block into the sample's "not
+// empty" flag before any corner is requested (include/nrnerf.h, "occupancy masks")
+struct NoMask {
+    static constexpr bool on = false;
+};
+struct BlockMask {
+    static constexpr bool on = true;
+    const unsigned* occ;     // bit (bz * nb[1] + by) * nb[0] + bx, word index >> 5, bit index & 31
+    int k;                   // log2 of the block's cells per axis
+    int nb[2];               // blocks along x, y
+    // the bit of the block of cell i: the block is i >> k per axis (grid_cell clamps i to 0 .. g - 2, so the block exists whether the sample is
+    // inside the box or not)
+    __device__ __forceinline__ bool bit(const int (&i)[3]) const {
+        const int blk = ((i[2] >> k) * nb[1] + (i[1] >> k)) * nb[0] + (i[0] >> k);
+        const unsigned word = ((const __attribute__((address_space(1))) unsigned*)occ)[blk >> 5];
+        return ((word >> (blk & 31)) & 1u) != 0u;
+    }
+};
+
+// where the point falls, and the requests for its eight corners (none for an empty sample, which a sample in an empty block of `mask` is)
+template <bool HALF, class MASK = NoMask>
+__device__ __forceinline__ void grid_fetch(const GridArgs& a, const float px, const float py, const float pz, GridFetch<HALF>& t,
+                                           const MASK mask = MASK{}) {
     typedef typename GridFetch<HALF>::vertex vertex;
     int i[3];
     grid_cell(a, px, py, pz, i, t.f, t.ok);
+    if constexpr (MASK::on) t.ok = t.ok && mask.bit(i);
 #pragma unroll
     for (int k = 0; k < 8; ++k) t.c[k] = vertex{};
     if (t.ok) {

@@ -15,11 +15,12 @@
 // warped_lookup_kernel<VHALF, WHALF>: the same per-sample rule, one thread per sample, no compositing.
 // No multiply-add is fused that the rule does not name: every product that feeds a sum goes through rounded() (nrnerf_volume_lookup.h).
 // bend / removed / sample_bent live in nrnerf_baked_sample.h, shared with nrnerf_sh_volume.hip and nrnerf_culled_volume.hip.
-// A COPY of warped_render_kernel with an occupancy bit in the sample's flag is culled_render_kernel (nrnerf_culled_volume.hip; this object
-// must keep exactly its kernels): a fix here belongs there too.
+// culled_render_kernel (nrnerf_culled_volume.hip) is warped_render_kernel's text with the point source as a parameter and the occupancy mask in
+// grid_fetch: two texts, because shared behind a function they measured slower.  The launch idiom: nrnerf_baked_launch.h.
 #include <hip/hip_runtime.h>
 
 #include "nrnerf_warp.h"
+#include "nrnerf_baked_launch.h"
 #include "nrnerf_composite_ray.h"
 #include "nrnerf_volume_lookup.h"
 #include "nrnerf_baked_sample.h"
@@ -28,17 +29,14 @@ namespace nrn {
 
 namespace {
 
-constexpr int WARP_WAVES = 4;           // waves (= rays in flight) per workgroup
-constexpr int WARP_MAXS = 1024;         // NRNERF_MAX_SAMPLES: EPL <= 16
-
 template <int EPL, bool VHALF, bool WHALF>
-__global__ void __launch_bounds__(WARP_WAVES * 64) warped_render_kernel(const WarpArgs a) {
-    constexpr int GROUP = EPL <= 4 ? EPL : (EPL == 6 ? 3 : (EPL == 16 ? 1 : 2));
+__global__ void __launch_bounds__(BAKED_WAVES * 64) warped_render_kernel(const WarpArgs a) {
+    constexpr int GROUP = gather_group(EPL);
     static_assert(EPL % GROUP == 0, "whole groups");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int S = a.c.S;
-    const long long step = (long long)gridDim.x * WARP_WAVES;
-    for (long long rr = (long long)blockIdx.x * WARP_WAVES + wave; rr < a.c.n_rays; rr += step) {
+    const long long step = (long long)gridDim.x * BAKED_WAVES;
+    for (long long rr = (long long)blockIdx.x * BAKED_WAVES + wave; rr < a.c.n_rays; rr += step) {
         const int ray = (int)rr;
         const __attribute__((address_space(1))) float* rp = gmem(a.c.rays) + (size_t)ray * a.c.ray_stride;
         f32x4 raw[EPL];
@@ -101,41 +99,22 @@ __global__ void __launch_bounds__(256) warped_lookup_kernel(const WarpArgs a) {
     }
 }
 
-template <class KERNEL>
-hipError_t launch(KERNEL kernel, const WarpArgs& a, const dim3 grid, const dim3 block, hipStream_t stream) {
-    hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
-    return hipGetLastError();
-}
-
-template <int EPL>
-hipError_t launch_epl(const WarpArgs& a, int num_cus, hipStream_t stream) {
-    const long long want = ((long long)a.c.n_rays + WARP_WAVES - 1) / WARP_WAVES, cap = (long long)(num_cus > 0 ? num_cus : 256) * 16;
-    const dim3 grid((unsigned)(want < cap ? want : cap)), block(WARP_WAVES * 64);
-    switch ((a.vol.half ? 2 : 0) | (a.warp.half ? 1 : 0)) {
-        case 0: return launch(warped_render_kernel<EPL, false, false>, a, grid, block, stream);
-        case 1: return launch(warped_render_kernel<EPL, false, true>, a, grid, block, stream);
-        case 2: return launch(warped_render_kernel<EPL, true, false>, a, grid, block, stream);
-        default: return launch(warped_render_kernel<EPL, true, true>, a, grid, block, stream);
-    }
-}
-
 }  // namespace
 
 hipError_t launch_warped_volume_render(const WarpArgs& a, int num_cus, hipStream_t stream) {
-    if (a.c.S < 1 || a.c.S > WARP_MAXS) return hipErrorInvalidValue;
+    if (a.c.S < 1 || a.c.S > BAKED_MAXS) return hipErrorInvalidValue;
     if (a.c.n_rays <= 0) return hipSuccess;
     if (!a.c.rgb) {                         // the lookup alone
         if (!a.raw_out && !a.points4_out) return hipErrorInvalidValue;
-        const long long want = ((long long)a.c.n_rays * a.c.S + 255) / 256, cap = (long long)(num_cus > 0 ? num_cus : 256) * 32;
-        const dim3 grid((unsigned)(want < cap ? want : cap)), block(256);
-        switch ((a.vol.half ? 2 : 0) | (a.warp.half ? 1 : 0)) {
-            case 0: return launch(warped_lookup_kernel<false, false>, a, grid, block, stream);
-            case 1: return launch(warped_lookup_kernel<false, true>, a, grid, block, stream);
-            case 2: return launch(warped_lookup_kernel<true, false>, a, grid, block, stream);
-            default: return launch(warped_lookup_kernel<true, true>, a, grid, block, stream);
-        }
+        return with_storage(a.vol.half, a.warp.half, [&](auto vh, auto wh) {
+            return launch(warped_lookup_kernel<vh(), wh()>, a, sample_grid(a.c.n_rays, a.c.S, num_cus), dim3(256), stream);
+        });
     }
-    return with_epl(a.c.S, [&](auto epl) { return launch_epl<epl()>(a, num_cus, stream); });
+    return with_epl(a.c.S, [&](auto epl) {
+        return with_storage(a.vol.half, a.warp.half, [&](auto vh, auto wh) {
+            return launch(warped_render_kernel<epl(), vh(), wh()>, a, ray_loop_grid(a.c.n_rays, num_cus), dim3(BAKED_WAVES * 64), stream);
+        });
+    });
 }
 
 }  // namespace nrn

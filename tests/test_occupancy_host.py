@@ -279,7 +279,9 @@ def test_occupancy_build_status_table(case, kw, want):
 
 # ---- 4. the code objects ---------------------------------------------------------------------------------------------------------------------------
 BUILD = os.path.join(REPO, "nonrigid_nerf_amd", "csrc", "build")
-OBJECTS = ["nrnerf_culled_volume_d0.o", "nrnerf_culled_volume_d1.o", "nrnerf_culled_volume_d2.o", "nrnerf_occupancy.o"]
+# (the unmasked kernels, whose text the culled ones follow line by line, are held to the same bounds)
+OBJECTS = ["nrnerf_culled_volume_d0.o", "nrnerf_culled_volume_d1.o", "nrnerf_culled_volume_d2.o", "nrnerf_occupancy.o",
+           "nrnerf_warp.o", "nrnerf_sh_volume_d1.o", "nrnerf_sh_volume_d2.o"]
 
 
 def occupancy_kernel_resources():
@@ -324,7 +326,10 @@ def test_every_kernel_of_the_new_objects_stays_within_256_registers_with_nothing
         assert r["scratch"] == 0 and r["vgpr_spill"] == 0, (o, name, r)
         assert r["vgpr"] <= 256 and r["agpr"] == 0, (o, name, r)          # (within the architectural VGPRs: nothing is parked in AGPRs either)
         m = (re.search(r"culled_(render)_kernelILi(\d+)ELb([01])ELi([012])ELb([01])E", name) or re.search(r"culled_(sh_render)_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E", name)
-             or re.search(r"culled_(lookup)_kernelILi(\d+)ELb([01])ELb([01])E", name) or re.search(r"(occupancy_build)_kernelILb([01])E", name))
+             or re.search(r"culled_(lookup)_kernelILi(\d+)ELb([01])ELb([01])E", name) or re.search(r"(occupancy_build)_kernelILb([01])E", name)
+             or re.search(r"(warped_render)_kernelILi(\d+)ELb([01])ELb([01])E", name) or re.search(r"(warped_lookup)_kernelILb([01])ELb([01])E", name)
+             or re.search(r"(?<=\d)(sh_render)_kernelILi(\d+)ELi(\d+)ELb([01])ELb([01])E", name)
+             or re.search(r"(?<=\d)(sh_lookup)_kernelILi(\d+)ELb([01])ELb([01])E", name))
         assert m is not None, name
         kinds.append((o, m.group(1)) + tuple(int(v) for v in m.groups()[1:]))
     # degree 0: (EPL, volume half, source: 0 straight / 1 points4_in / 2 warp, warp half); without a warp its storage is no parameter
@@ -333,6 +338,9 @@ def test_every_kernel_of_the_new_objects_stays_within_256_registers_with_nothing
     want += [(f"nrnerf_culled_volume_d{d}.o", "sh_render", d, e, v, w) for d in (1, 2) for e in epls for v, w in halves]
     want += [(f"nrnerf_culled_volume_d{d}.o", "lookup", d, v, w) for d in (0, 1, 2) for v, w in halves]
     want += [("nrnerf_occupancy.o", "occupancy_build", h) for h in (0, 1)]
+    want += [("nrnerf_warp.o", "warped_render", e, v, w) for e in epls for v, w in halves] + [("nrnerf_warp.o", "warped_lookup", v, w) for v, w in halves]
+    want += [(f"nrnerf_sh_volume_d{d}.o", "sh_render", d, e, v, w) for d in (1, 2) for e in epls for v, w in halves]
+    want += [(f"nrnerf_sh_volume_d{d}.o", "sh_lookup", d, v, w) for d in (1, 2) for v, w in halves]
     assert sorted(kinds) == sorted(want)
 
 
